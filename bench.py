@@ -1,6 +1,10 @@
 """Stage-1 projector-step benchmark (BASELINE.json metric: images/sec/node).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--full` adds what takes runs
+of its own (the CPU baselines and their thread sweep; `--no-cpu-baseline` leaves them out again).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy.
 
 N>1 runs as one process per GPU (RCCL): under `torch.distributed.run` the
 launcher's WORLD_SIZE must equal N; without a launcher bench.py starts
@@ -38,7 +42,15 @@ def _args(argv=None):
     ap.add_argument("--config", default="cfg2")
     ap.add_argument("--batch", type=int, default=None, help="per-GPU batch (default: the config's)")
     ap.add_argument("--text-len", type=int, default=None, help="text tokens T (default: the config's)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baselines (oracle on this host, "
+                         "cfg1, thread sweep); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last of them computed (loss, grad norm, updated "
+                         "parameters, grads) as DIR/<name>.npy, float32; arrays above 4 Mi elements as a fixed "
+                         "seeded sample.  Same arguments = same inputs, so two builds compare output for output")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: leave the CPU baselines out")
     ap.add_argument("--cpu-baseline-only", action="store_true",
                     help="time only the CPU baseline (no GPU) and print it")
     ap.add_argument("--prefetch", action="store_true",
@@ -247,6 +259,26 @@ def geglu_label(census, steps):
             f"layer's launch on the B*T loss rows, 2*(B*T)*(2I)*H); achieved = summed FLOP / summed event time")
 
 
+DUMP_MAX_ELEMS = 4 << 20     # per array: 16 MiB as float32, so the few arrays of a step stay far below 64 MB
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every tensor of `arrays` as DIR/<name>.npy in float32 (float64 stays float64).  A tensor
+    of more than DUMP_MAX_ELEMS elements is written as the sample at DUMP_MAX_ELEMS sorted indices drawn once
+    from a generator seeded with 0: the same indices for the same element count, run after run."""
+    import numpy as np
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    for name, t in arrays.items():
+        t = t.detach().reshape(-1)
+        if t.numel() > DUMP_MAX_ELEMS:
+            g = torch.Generator().manual_seed(0)
+            idx = torch.randint(0, t.numel(), (DUMP_MAX_ELEMS,), generator=g).sort().values
+            t = t[idx.to(t.device)]
+        t = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu()
+        np.save(os.path.join(dirname, name + ".npy"), t.numpy())
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = _args(argv)
@@ -330,6 +362,11 @@ def main(argv=None):
     if world > 1:
         dist.barrier()
     t_wall = time.perf_counter() - t_wall
+    if args.dump_outputs and rank == 0:
+        # the caller's view of the last timed step: its loss, and the projector's grads, clip norm and
+        # updated parameters
+        dump_outputs(args.dump_outputs, {"loss": loss, "grad_norm": eng.grad_norm,
+                                         "projector_grad": eng.proj.flat_grad, "projector_param": eng.proj.flat})
     if graph:
         L.lib().ptk_gemm_timer_enable((1 << 8) | (1 << L.ACT_GEGLU))
         eng.step(px, ids, labels)
@@ -416,7 +453,7 @@ def main(argv=None):
         L.stage_timers_enable(False)
         line["stages_ms_per_step"] = {k: round(ms / args.steps, 4)
                                       for k, (ms, n) in L.stage_timers_read(reset=True).items()}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(args.config)
         cb1 = cpu_baseline("cfg1", seconds_budget=20.0)
         line["cpu_baseline_cfg1"] = {k: cb1[k] for k in ("value", "unit", "cores", "kind", "sample")}
@@ -487,6 +524,9 @@ def bench_stage2(args, cfg, world, rank, dev):
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
+    if args.dump_outputs and rank == 0:
+        # the caller's view of the last timed step: its loss, the clip norm and the updated Gemma3 weights
+        dump_outputs(args.dump_outputs, {"loss": loss, "grad_norm": eng.grad_norm, "llm_param": eng.state.flat})
     elapsed = ev[0].elapsed_time(ev[-1]) / 1e3
     med_ms = float(np.median([ev[k].elapsed_time(ev[k + 1]) for k in range(args.steps)]))
     L.lib().ptk_gemm_timer_enable(0)

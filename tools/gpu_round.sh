@@ -4,7 +4,7 @@
 # parts (default: tests smoke bench prof): tests | smoke | bench | stages | cfg5 | cfg4 | prof | pmc
 #   tests   full `pytest -m gpu` (TESTS=<pytest args> / KEXPR=<-k expression> select a subset)
 #   smoke   __graft_entry__.smoke()
-#   bench   default bench.py line (with the CPU baseline)
+#   bench   bench.py --full line (with the CPU baseline)
 #   stages  bench.py --stage-timers (per-stage breakdown)
 #   cfg5 / cfg4   the Gemma3-4B Stage-1 and the Stage-2 bench lines
 #   prof    rocprofv3 --kernel-trace --stats of bench.py (kernel statistics CSV)
@@ -32,7 +32,7 @@ for part in "${PARTS[@]}"; do
       timeout -k 10 200 python -u -c "import __graft_entry__ as g; g.smoke()" > $log 2>&1 || fail smoke $? $log
       grep smoke: $log ;;
     bench)
-      timeout -k 10 600 python -u bench.py > $log 2>&1 || fail bench $? $log
+      timeout -k 10 600 python -u bench.py --full > $log 2>&1 || fail bench $? $log
       tail -1 $log | cut -c1-400 ;;
     stages)
       timeout -k 10 300 python -u bench.py --steps 10 --warmup 3 --no-cpu-baseline --stage-timers > $log 2>&1 || fail stages $? $log
