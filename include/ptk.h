@@ -92,6 +92,18 @@ int ptk_gemm(const ptk_gemm_desc* d, void* stream);
 size_t ptk_gemm_tail_scratch_bytes(void);
 /* Workgroups the stream-K plan spreads this GEMM's last tile round over (0: no split), for tests. */
 int ptk_gemm_tail_split(const ptk_gemm_desc* d);
+/* For tests: what ptk_gemm would dispatch this descriptor to on a device of ncu compute units, without launching
+ * anything (the host-side dispatch planner alone, so it answers on a machine without a GPU).  It uses the current
+ * force mode (ptk_gemm_force_small_tiles) and the descriptor's tail_ws as the only tail scratch.  path: the kernel
+ * family as ptk_gemm_path_counts numbers them; tile_rows: 256, or 224 / 192 / 160 on the persistent 8-wave kernel;
+ * tail_split: the workgroups sharing the stream-K tail (0: none).  Any output pointer may be NULL. */
+int ptk_gemm_plan(const ptk_gemm_desc* d, int ncu, int* path, int* tile_rows, int* tail_split);
+/* For tests: how the model-level calls split this plain GEMM (d->out bf16 or fp32) along K given part_floats floats
+ * of fp32 scratch.  *kc == 0: one unsplit launch (*tail_ws != 0: with the scratch lent to the stream-K tail);
+ * otherwise *slices partial GEMMs of depth *kc (possibly one), plus one of depth *rem when *rem != 0, summed in
+ * slice order. */
+int ptk_gemm_split_plan(const ptk_gemm_desc* d, int ncu, int64_t part_floats, int* slices, int* kc, int* rem,
+                        int* tail_ws);
 
 /* LayerNorm (SigLIP, modeling_siglip.py:329): x f32 [rows,cols] -> y bf16. */
 int ptk_layernorm(const float* x, const float* w, const float* b, void* y, int rows, int cols, float eps,

@@ -142,6 +142,8 @@ SIGNATURES = {
     "ptk_gemm": (c_int, [C.POINTER(GemmDesc), c_void_p]),
     "ptk_gemm_tail_scratch_bytes": (c_size_t, []),
     "ptk_gemm_tail_split": (c_int, [C.POINTER(GemmDesc)]),
+    "ptk_gemm_plan": (c_int, [C.POINTER(GemmDesc), c_int] + [C.POINTER(c_int)] * 3),
+    "ptk_gemm_split_plan": (c_int, [C.POINTER(GemmDesc), c_int, c_int64] + [C.POINTER(c_int)] * 4),
     "ptk_layernorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "ptk_rmsnorm": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_void_p]),
     "ptk_rmsnorm_bwd": (c_int, [c_void_p] * 6 + [c_int, c_int, c_void_p]),

@@ -38,6 +38,20 @@ GemmArgs to_args(const ptk_gemm_desc* d) {
   return a;
 }
 
+// compute units of the current device: the library's one cache (256 when no device answers)
+int device_cus() {
+  static int n = 0;
+  if (n == 0) {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) == hipSuccess &&
+        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
+      n = v;
+    else
+      n = 256;
+  }
+  return n;
+}
+
 }  // namespace ptk
 
 using namespace ptk;
@@ -57,7 +71,34 @@ int ptk_gemm(const ptk_gemm_desc* d, void* stream) {
 size_t ptk_gemm_tail_scratch_bytes(void) { return p8_tail_scratch_bytes(); }
 int ptk_gemm_tail_split(const ptk_gemm_desc* d) {
   if (!d) return set_error("ptk_gemm_tail_split: null desc");
-  return p8_tail_split(to_args(d), d->act, d->out);
+  // the planner's tail plan over the descriptor's or the scope's scratch, without launch_gemm's M / N / batch gates
+  return p8_tail_plan(to_args(d), d->act, d->out, gemm_plan_env()).gsplit;
+}
+// the planner's answers under the current force mode, with the descriptor's tail_ws as the only scratch (no
+// model-level scope), on a device of ncu compute units: nothing is launched, so they hold without a GPU
+static GemmPlanEnv test_plan_env(int ncu) {
+  GemmPlanEnv e = gemm_plan_env();
+  e.ncu = ncu;
+  e.tail_scope = nullptr;
+  return e;
+}
+int ptk_gemm_plan(const ptk_gemm_desc* d, int ncu, int* path, int* tile_rows, int* tail_split) {
+  if (!d || ncu <= 0) return set_error("ptk_gemm_plan: null desc or ncu <= 0");
+  const GemmPlan p = gemm_plan(to_args(d), d->act, d->out, d->batch > 0 ? d->batch : 1, test_plan_env(ncu));
+  if (path) *path = p.path;
+  if (tile_rows) *tile_rows = p.tm;
+  if (tail_split) *tail_split = p.tail.gsplit;
+  return 0;
+}
+int ptk_gemm_split_plan(const ptk_gemm_desc* d, int ncu, int64_t part_floats, int* slices, int* kc, int* rem,
+                        int* tail_ws) {
+  if (!d || ncu <= 0) return set_error("ptk_gemm_split_plan: null desc or ncu <= 0");
+  const GemmSplitPlan s = gemm_split_plan(to_args(d), d->out, (long)part_floats, test_plan_env(ncu));
+  if (slices) *slices = s.slices;
+  if (kc) *kc = s.kc;
+  if (rem) *rem = s.rem;
+  if (tail_ws) *tail_ws = s.tail_ws ? 1 : 0;
+  return 0;
 }
 
 size_t ptk_gemm_skinny_part_bytes(int M, int N, int K) { return skinny_part_bytes(M, N, K); }
@@ -242,7 +283,7 @@ int projector_bwd_stage(const ptk_projector* p, int rows, const void* x, const v
     GemmArgs g;
     g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.C = C; g.M = M; g.N = N; g.K = Rp;
     g.lda = lda; g.ldb = ldb; g.ldc = N;
-    if (!tn_supported(g, OUT_F32, 1)) return 1;
+    if (!tn_supported(g, OUT_F32, 1, lean_epilogue_enabled())) return 1;
     return gemm_tn(g, OUT_F32, 1, nullptr, st, R) ? -1 : 0;
   };
   if (stage == 0) {

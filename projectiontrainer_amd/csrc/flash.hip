@@ -2385,22 +2385,9 @@ __global__ void __launch_bounds__(256) attn_dkv_reduce_kernel(FlashBwdArgs a) {
   *reinterpret_cast<u16x4_t*>(out) = u;
 }
 
-static int num_cus() {
-  static int n = 0;
-  if (n == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess &&
-        hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-      n = v;
-    else
-      n = 256;
-  }
-  return n;
-}
-
 // Split plan.  Each block (one slab piece of one z) costs its query chunks plus a fixed overhead
 // (K/V fragment loads, ring fill, dK/dV stores; ~1.5 chunks) and, for a piece of a split slab, the
-// fp32 partial store (~1 chunk).  Blocks are dispatched heaviest first (LPT) onto num_cus() CUs
+// fp32 partial store (~1 chunk).  Blocks are dispatched heaviest first (LPT) onto device_cus() CUs
 // (one block per CU: 129 KiB LDS); the target piece size is the candidate whose simulated makespan
 // is smallest (causal slabs differ up to 11x, so one-piece-per-CU targets leave a third of the
 // machine idle in the tail).
@@ -2440,7 +2427,7 @@ static void dkv_plan(FlashBwdArgs& a, int nz, int& nslab, long& npieces, long& n
     dkv_slab_chunks(a, s, lo, hi);
     total += hi - lo;
   }
-  const int ncu = num_cus();
+  const int ncu = device_cus();
   // the work-item table holds 128 (slab, piece) entries: a target is admissible only if its pieces fit
   auto items_for = [&](int t) {
     long items = 0;
@@ -2532,7 +2519,7 @@ int launch_attn_bwd(const FlashBwdArgs& a, int nz, hipStream_t st, FlashBwdArgs*
         // item's prologue beside this one's epilogue); PTK_ATTN_PERSIST=0 (A/B builds): one workgroup per item
         const bool persist = PTK_AB("PTK_ATTN_PERSIST", 1) != 0;
         const long nblk = (long)gq.x;
-        const long g = persist ? std::min<long>(nblk, num_cus()) : nblk;
+        const long g = persist ? std::min<long>(nblk, device_cus()) : nblk;
         hipLaunchKernelGGL(attn_bwd_dq256w_kernel, dim3((unsigned)g), dim3(256), 0, st, b, nz, (int)nblk);
       }
       else hipLaunchKernelGGL(attn_delta_kernel<256>, gd, dim3(256), 0, st, b, nz);
@@ -2587,7 +2574,7 @@ int launch_attn_fwd(const FlashArgs& a, int nz, hipStream_t st) {
         // persistent grid (one workgroup per CU walking the row blocks heaviest first, the next item's prologue
         // beside this one's epilogue); PTK_ATTN_PERSIST=0 (A/B builds): one workgroup per item (A/B, bit-identical)
         const bool persist = PTK_AB("PTK_ATTN_PERSIST", 1) != 0;
-        const long g = persist ? std::min<long>(nblk, num_cus()) : nblk;
+        const long g = persist ? std::min<long>(nblk, device_cus()) : nblk;
         hipLaunchKernelGGL(attn_fwd256w_kernel, dim3((unsigned)g), dim3(256), 0, st, a, nz, (int)nblk);
       }
       break;

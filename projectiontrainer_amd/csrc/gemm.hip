@@ -700,17 +700,6 @@ __global__ void __launch_bounds__(512, 1) gemm_big2_kernel(GemmArgs p) {
   big_epilogue<ACT, OUT>(p, smem, bm, bn, acc, threadIdx.x);
 }
 
-static int g_num_cu = 0;
-static int num_cus() {
-  if (!g_num_cu) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256;
-    g_num_cu = prop.multiProcessorCount;
-  }
-  return g_num_cu;
-}
-
 // ---- optional live per-class timing (HIP events around launches; bench.py roofline)
 static bool g_timing = false;
 static int g_timing_mask = 0;   // activation classes whose launches are timed
@@ -751,17 +740,6 @@ int timer_read(int cls, double* total_ms, int* count) {
   return 0;
 }
 
-#define PTK_GEMM_CASE(ACT_, OUT_)                                                              \
-  if (act == ACT_ && out == OUT_) {                                                            \
-    hipEvent_t e0 = nullptr, e1 = nullptr;                                                     \
-    if (g_timing && ((g_timing_mask >> act) & 1)) { e0 = next_event(act); e1 = next_event(act); }                              \
-    if (e0) (void)hipEventRecord(e0, st);                                                          \
-    count_path(batch > 1 ? GEMM_PATH_NTB : GEMM_PATH_NT, act);                                 \
-    hipLaunchKernelGGL((gemm_nt_kernel<ACT_, OUT_>), grid, dim3(256), 0, st, a);              \
-    if (e1) (void)hipEventRecord(e1, st);                                                          \
-    return hipGetLastError() == hipSuccess ? 0 : set_error("gemm launch failed");             \
-  }
-
 // Dispatch census (tests assert which kernel family a model-level call ran): launches per (path, act)
 static long g_path_count[GEMM_NPATH][8];
 int path_counts(int64_t* out, int reset) {
@@ -772,9 +750,35 @@ int path_counts(int64_t* out, int reset) {
     }
   return 0;
 }
-static inline void count_path(int path, int act) { ++g_path_count[path][act & 7]; }
 
-int launch_gemm(const GemmArgs& a, int act, int out, int batch, hipStream_t st) {
+// one GEMM launch's census count and optional HIP event pair (live timers): count, record e0, launch, record e1
+struct GemmLaunchScope {
+  hipStream_t st;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  GemmLaunchScope(int path, int act, hipStream_t s) : st(s) {
+    ++g_path_count[path][act & 7];
+    if (g_timing && ((g_timing_mask >> act) & 1)) { e0 = next_event(act); e1 = next_event(act); }
+    if (e0) (void)hipEventRecord(e0, st);
+  }
+  ~GemmLaunchScope() { if (e1) (void)hipEventRecord(e1, st); }
+};
+
+// what the planner may depend on besides the operands (gemm_plan.cpp reads no globals): the force mode, the A/B
+// switches (PTK_P8=1: every w4 shape on the 8-wave kernel; PTK_TM224=0: 256-row tiles only), the lent tail scratch
+GemmPlanEnv gemm_plan_env() {
+  GemmPlanEnv e;
+  e.ncu = device_cus();
+  e.force_tiles = g_force_tiles;
+  e.p8_all = PTK_AB("PTK_P8", 0) == 1;
+  e.tm_short = PTK_AB("PTK_TM224", 1) != 0;
+  e.lean_epi = lean_epilogue_enabled();
+  e.streamk = streamk_enabled();
+  e.tail_scope = tail_scope();
+  return e;
+}
+
+// plan (gemm_plan.cpp: the shape rule) -> launch
+int launch_gemm(const GemmArgs& a, int act, int out, int batch, hipStream_t st, const GemmPlan* planned) {
   if (a.M <= 0 || a.N <= 0 || batch <= 0) return 0;
   if (a.K <= 0 || a.K % BK) return set_error("gemm: K=%d must be a positive multiple of 64", a.K);
   if ((a.lda % 8) || (a.ldb % 8)) return set_error("gemm: lda/ldb must be multiples of 8 (16-B rows)");
@@ -782,166 +786,45 @@ int launch_gemm(const GemmArgs& a, int act, int out, int batch, hipStream_t st) 
   if (a.zin <= 0) return set_error("gemm: zin must be >= 1");
   const long ntile = (long)((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
   if (ntile > 0x7fffffffL) return set_error("gemm: too many tiles");
-  // 256x256 (one block per CU) only where the K loop amortises its lock-step epilogue: long K or
-  // wide N at K >= 1152.  Elsewhere two co-resident 128x128 blocks per CU overlap one block's
-  // epilogue with the other's MFMA and quantise better (tools/gemm_bench.py --all, r01).
-  // long K: the barrier-staggered 256x256 variant (+6-7 % at K >= 4096, tools/gemm_bench.py --all)
-  const bool big_shape = a.M >= 1024 && a.N >= 512 && (a.K >= 6144 || (a.N >= 6144 && a.K >= 1152));
-  // persistent 4-wave 256x256 kernel (gemm_w4.hip) where it measured ahead of the 8-wave and
-  // 128x128 kernels (tools/gemm_bench.py --all, same box, r01): the GEGLU gate|up projection, and
-  // plain projections (bf16 or fp32 out, K <= 8192) whose 256x256 tiles fill >= 80 % of the
-  // persistent grid's rounds (SigLIP qkv +4 %, Gemma o +6 %, dh +17 %, down +3 %, dqkv +2 %).  Not the
-  // N = 1024 / 1536 shapes (352 / 528 tiles: 69 % round fill, the 128x128 kernel wins), the
-  // vocab-wide lm_head, the K = 11520 / 13824 projections or the GELU epilogues
-  // (r02: + the GELU-tanh epilogue with packed f32 math, SigLIP fc1 887 -> 936 TFLOP/s, tools/gemm_bench.py --all)
-  const bool w4_auto = g_force_tiles == 0 && a.M >= 4096 && a.N <= 16384 &&
-                       (act == ACT_GEGLU || act == ACT_GEGLU_BWD ||
-                        (((act == ACT_NONE && (out == OUT_BF16 || out == OUT_F32)) ||
-                          (act == ACT_GELU_TANH && out == OUT_BF16)) &&
-                         a.K <= 8192 && w4_round_fill(a.M, a.N) >= 0.8));
-  // persistent 8-wave kernel (two waves per SIMD, gemm_w4.hip) where it measured ahead of the 4-wave one
-  // (tools/p8_probe.py, same box, interleaved, r03): the w4 plain / GELU-tanh shapes at K <= 2048 (Gemma q|k|v
-  // 90 -> 87 us, o 58 -> 56, SigLIP q|k|v 111 -> 109, fc1 157 -> 151), the projector fc1 with the GELU-erf
-  // epilogue (674 -> 583 us) and its backward (dA, 858 -> 703 us) and the long-K d(gate|up) dX (K 13 824, N <= 2048: 700 -> 672 us); w4 keeps the
-  // GEGLU / GEGLU-backward epilogues and the K 6 912 down projection (697 / 486 / 330 us vs 723 / 500 / 342).
-  // PTK_P8=1 (A/B builds, PTK_AB) puts every w4 shape on it
-  const bool p8_env = PTK_AB("PTK_P8", 0) == 1;
-  const bool p8_auto = g_force_tiles == 0 && a.M >= 4096 && a.N <= 16384 &&
-                       ((w4_auto && (p8_env || (act != ACT_GEGLU && act != ACT_GEGLU_BWD && a.K <= 2048))) ||
-                        ((act == ACT_GELU_ERF || act == ACT_GELU_ERF_BWD) && out == OUT_BF16 && a.K <= 2048 &&
-                         w4_round_fill(a.M, a.N) >= 0.8) ||
-                        (act == ACT_NONE && (out == OUT_BF16 || out == OUT_F32) && a.K >= 12288 && a.N <= 2048) ||
-                        // r05: with the lean bf16 epilogue the 8-wave kernel also beats the 128x128 one on the N 1536
-                        // projection at 69 % round fill (Gemma q|k|v 90.7 vs 95.3 us, profiles/r05_dual_solo_probe.txt);
-                        // the N 1024 ones stay on 128x128 (dO 66.0 vs 63.2, SigLIP fc2 187 vs 171)
-                        (act == ACT_NONE && out == OUT_BF16 && a.N >= 1536 && a.K <= 2048 &&
-                         w4_round_fill(a.M, a.N) >= 0.65 && lean_epilogue_candidate(a)) ||
-                        // r05: a plain bf16 grid of one partial round of 256x256 tiles beats the 128x128 kernel's
-                        // ~1.1 rounds of two blocks per CU (tools/sk_ab.py, Stage 2's SigLIP at M = 9 216: o 31.3 vs
-                        // 41.8 us, fc2 85.1 vs 109.1; its down projection at bs 8 133.6 vs 177.8)
-                        (act == ACT_NONE && out == OUT_BF16 && a.K <= 8192 &&
-                         (long)((a.M + 255) / 256) * ((a.N + 255) / 256) <= device_cus() && lean_epilogue_candidate(a)));
-  // the stream-K tail (gemm_w4.hip P8Tail): a plain GEMM whose last tile round fills the CUs badly, with tail
-  // scratch lent by the model-level call (or in the descriptor), runs on the persistent 8-wave kernel with that
-  // round's K-tiles spread over the CUs (r04: the N = 1024 / 1152 / 1536 projections, the long-K d(gate|up) dX
-  // and down projection, the projector's fc2 and weight grads)
-  const int sk = (g_force_tiles == 0 || g_force_tiles == 32) && batch == 1 && act == ACT_NONE && a.M >= 1024 &&
-                 a.N >= 256 && a.N <= 16384 && p8_supported(a, act, out) ? p8_tail_split(a, act, out) : 0;
-  // (the two-group persistent kernel on 256x128 tiles, gemm_dual.hip, measured 17-44 % slower than the 8-wave
-  // kernel in round 5, profiles/r05_dual_probe.txt, and was removed from the tree in round 6)
-  // 224- / 192-row tiles on the 8-wave kernel where their rounds undercut the 256-row ones (p8_tile_height:
-  // Gemma3's N 1152 / 1536 / 1024 projections at M 22 528, SigLIP's q|k|v, o and fc1 at M 18 432), ahead of the
-  // 4-wave and 128x128 kernels; force modes 512 / 1024 put every plain / GELU-tanh single GEMM on 224 / 192 rows
-  // (tests).  PTK_TM224=0 (A/B builds, PTK_AB): 256-row tiles only
-  const bool tm_env = PTK_AB("PTK_TM224", 1) != 0;
-  const bool short_ok = batch == 1 && !sk && p8_supported(a, act, out) &&
-                        (act == ACT_NONE || (act == ACT_GELU_TANH && out == OUT_BF16));
-  int tm = 256;
-  if (short_ok && g_force_tiles == 0 && tm_env && a.M >= 4096) tm = p8_tile_height(a, act, out);
-  else if (short_ok && g_force_tiles == 512) tm = 224;
-  else if (short_ok && g_force_tiles == 1024) tm = 192;
-  else if (short_ok && g_force_tiles == 4096) tm = 160;
-  if (batch == 1 && (g_force_tiles == 32 || p8_auto || sk || tm != 256) && p8_supported(a, act, out)) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (g_timing && ((g_timing_mask >> act) & 1)) { e0 = next_event(act); e1 = next_event(act); }
-    if (e0) (void)hipEventRecord(e0, st);
-    count_path(sk ? GEMM_PATH_P8SK : GEMM_PATH_P8, act);
-    const int rc = launch_gemm_p8(a, act, out, st, sk != 0, tm);
-    if (e1) (void)hipEventRecord(e1, st);
-    return rc;
+  if (!gemm_act_out(act, out, [](auto, auto) {})) return set_error("gemm: unsupported (act=%d, out=%d)", act, out);
+  const GemmPlan plan = planned ? *planned : gemm_plan(a, act, out, batch, gemm_plan_env());
+  GemmLaunchScope scope(plan.path, act, st);
+  const dim3 grid_big((unsigned)((long)((a.M + BIG - 1) / BIG) * ((a.N + BIG - 1) / BIG)), 1, 1);
+  switch (plan.path) {
+    case GEMM_PATH_P8:
+    case GEMM_PATH_P8SK: return launch_gemm_p8(a, act, out, st, plan.tail, plan.tm);
+    case GEMM_PATH_W4: return launch_gemm_w4(a, act, out, st, 0);
+    case GEMM_PATH_BIG2:
+      gemm_act_out(act, out, [&](auto A, auto O) {
+        hipLaunchKernelGGL((gemm_big2_kernel<A(), O()>), grid_big, dim3(512), 0, st, a);
+      });
+      break;
+    case GEMM_PATH_BIG:
+      gemm_act_out(act, out, [&](auto A, auto O) {
+        hipLaunchKernelGGL((gemm_big_kernel<A(), O()>), grid_big, dim3(512), 0, st, a);
+      });
+      break;
+    default:   // GEMM_PATH_NT, GEMM_PATH_NTB
+      gemm_act_out(act, out, [&](auto A, auto O) {
+        hipLaunchKernelGGL((gemm_nt_kernel<A(), O()>), dim3((unsigned)ntile, 1, (unsigned)batch), dim3(256), 0, st, a);
+      });
+      break;
   }
-  if (batch == 1 && (g_force_tiles == 8 || w4_auto) && w4_supported(a, act, out)) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (g_timing && ((g_timing_mask >> act) & 1)) { e0 = next_event(act); e1 = next_event(act); }
-    if (e0) (void)hipEventRecord(e0, st);
-    count_path(GEMM_PATH_W4, act);
-    const int rc = launch_gemm_w4(a, act, out, st, 0);
-    if (e1) (void)hipEventRecord(e1, st);
-    return rc;
-  }
-  if (batch == 1 && (g_force_tiles == 4 || (g_force_tiles == 0 && big_shape && a.K >= 4096))) {
-    const long nb = (long)((a.M + BIG - 1) / BIG) * ((a.N + BIG - 1) / BIG);
-    dim3 g4((unsigned)nb, 1, 1);
-#define PTK_BIG2_CASE(ACT_, OUT_)                                                               \
-    if (act == ACT_ && out == OUT_) {                                                           \
-      hipEvent_t e0 = nullptr, e1 = nullptr;                                                    \
-      if (g_timing && ((g_timing_mask >> act) & 1)) { e0 = next_event(act); e1 = next_event(act); }                             \
-      if (e0) (void)hipEventRecord(e0, st);                                                     \
-      count_path(GEMM_PATH_BIG2, act);                                                          \
-      hipLaunchKernelGGL((gemm_big2_kernel<ACT_, OUT_>), g4, dim3(512), 0, st, a);              \
-      if (e1) (void)hipEventRecord(e1, st);                                                     \
-      return hipGetLastError() == hipSuccess ? 0 : set_error("gemm launch failed");            \
-    }
-    PTK_BIG2_CASE(ACT_NONE, OUT_BF16)
-    PTK_BIG2_CASE(ACT_NONE, OUT_F32)
-    PTK_BIG2_CASE(ACT_NONE, OUT_F32_BFR)
-    PTK_BIG2_CASE(ACT_GELU_TANH, OUT_BF16)
-    PTK_BIG2_CASE(ACT_GELU_ERF, OUT_BF16)
-    PTK_BIG2_CASE(ACT_GEGLU, OUT_BF16)
-    PTK_BIG2_CASE(ACT_GELU_ERF_BWD, OUT_BF16)
-    PTK_BIG2_CASE(ACT_GEGLU_BWD, OUT_BF16)
-#undef PTK_BIG2_CASE
-    return set_error("gemm: unsupported (act=%d, out=%d)", act, out);
-  }
-  const bool big = batch == 1 && g_force_tiles != 1 && (g_force_tiles == 2 || big_shape);
-  if (big) {
-    const long nb = (long)((a.M + BIG - 1) / BIG) * ((a.N + BIG - 1) / BIG);
-    dim3 g2((unsigned)nb, 1, 1);
-#define PTK_BIG_CASE(ACT_, OUT_)                                                                \
-    if (act == ACT_ && out == OUT_) {                                                           \
-      hipEvent_t e0 = nullptr, e1 = nullptr;                                                    \
-      if (g_timing && ((g_timing_mask >> act) & 1)) { e0 = next_event(act); e1 = next_event(act); }                             \
-      if (e0) (void)hipEventRecord(e0, st);                                                     \
-      count_path(GEMM_PATH_BIG, act);                                                           \
-      hipLaunchKernelGGL((gemm_big_kernel<ACT_, OUT_>), g2, dim3(512), 0, st, a);               \
-      if (e1) (void)hipEventRecord(e1, st);                                                     \
-      return hipGetLastError() == hipSuccess ? 0 : set_error("gemm launch failed");            \
-    }
-    PTK_BIG_CASE(ACT_NONE, OUT_BF16)
-    PTK_BIG_CASE(ACT_NONE, OUT_F32)
-    PTK_BIG_CASE(ACT_NONE, OUT_F32_BFR)
-    PTK_BIG_CASE(ACT_GELU_TANH, OUT_BF16)
-    PTK_BIG_CASE(ACT_GELU_ERF, OUT_BF16)
-    PTK_BIG_CASE(ACT_GEGLU, OUT_BF16)
-    PTK_BIG_CASE(ACT_GELU_ERF_BWD, OUT_BF16)
-    PTK_BIG_CASE(ACT_GEGLU_BWD, OUT_BF16)
-#undef PTK_BIG_CASE
-    return set_error("gemm: unsupported (act=%d, out=%d)", act, out);
-  }
-  dim3 grid((unsigned)ntile, 1, (unsigned)batch);
-  PTK_GEMM_CASE(ACT_NONE, OUT_BF16)
-  PTK_GEMM_CASE(ACT_NONE, OUT_F32)
-  PTK_GEMM_CASE(ACT_NONE, OUT_F32_BFR)
-  PTK_GEMM_CASE(ACT_GELU_TANH, OUT_BF16)
-  PTK_GEMM_CASE(ACT_GELU_ERF, OUT_BF16)
-  PTK_GEMM_CASE(ACT_GEGLU, OUT_BF16)
-  PTK_GEMM_CASE(ACT_GELU_ERF_BWD, OUT_BF16)
-  PTK_GEMM_CASE(ACT_GEGLU_BWD, OUT_BF16)
-  return set_error("gemm: unsupported (act=%d, out=%d)", act, out);
+  return hipGetLastError() == hipSuccess ? 0 : set_error("gemm launch failed");
 }
 
 // the K-sliced 8-wave GEMM (gemm_w4.hip launch_gemm_p8_kslices) with launch_gemm's census ("p8") and timers
 int gemm_p8_kslices(const GemmArgs& a, int slices, hipStream_t st) {
   if (a.M <= 0 || a.N <= 0) return 0;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (g_timing && (g_timing_mask & 1)) { e0 = next_event(ACT_NONE); e1 = next_event(ACT_NONE); }
-  if (e0) (void)hipEventRecord(e0, st);
-  count_path(GEMM_PATH_P8, ACT_NONE);
-  const int rc = launch_gemm_p8_kslices(a, slices, st);
-  if (e1) (void)hipEventRecord(e1, st);
-  return rc;
+  GemmLaunchScope scope(GEMM_PATH_P8, ACT_NONE, st);
+  return launch_gemm_p8_kslices(a, slices, st);
 }
 
 // the token-major weight-grad GEMM (gemm_tn.hip) with launch_gemm's census and live timers (class ACT_NONE)
 int gemm_tn(const GemmArgs& a, int out, int slices, void* slab, hipStream_t st, long k_rows) {
   if (a.M <= 0 || a.N <= 0) return 0;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (g_timing && (g_timing_mask & 1)) { e0 = next_event(ACT_NONE); e1 = next_event(ACT_NONE); }
-  if (e0) (void)hipEventRecord(e0, st);
-  count_path(GEMM_PATH_TN, ACT_NONE);
-  const int rc = launch_gemm_tn(a, out, slices, slab, st, k_rows);
-  if (e1) (void)hipEventRecord(e1, st);
-  return rc;
+  GemmLaunchScope scope(GEMM_PATH_TN, ACT_NONE, st);
+  return launch_gemm_tn(a, out, slices, slab, st, k_rows);
 }
 
 }  // namespace ptk

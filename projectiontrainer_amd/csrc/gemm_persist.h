@@ -21,29 +21,11 @@ namespace ptk {
 
 typedef __attribute__((ext_vector_type(4))) unsigned int u32x4v_t;
 
-// stream-K tail of the persistent 8-wave kernels (gemm_w4.hip gemm_p8_kernel, gemm_tn.hip gemm_tn_kernel): the
-// plan (p8_tail_plan) and the fixup that sums the cut tiles' pieces (launch_p8_fixup), described in gemm_w4.hip
-struct P8Tail {
-  int dp_tiles = 0;           // tiles [0, dp_tiles) run whole (R rounds of G)
-  int units = 0;              // U = tail tiles x K-tile pairs (0: no tail split)
-  int gsplit = 0;             // Gs: workgroups sharing the tail
-  float* slab = nullptr;      // [G][2 slots][8 waves][128 x 64] fp32 partials
-  // K slices as extra row tiles (no tail split): the grid's M = zslices x the real M; virtual row tile bm covers
-  // real rows (bm % (nbm / zslices)) x 256 and K rows [z K, (z + 1) K) of the operands (z = bm / (nbm / zslices)),
-  // so slice z's fp32 partial lands at output rows z M_real .. (gemm_p8_kslices)
-  int zslices = 1;
-};
-constexpr size_t P8_WAVE_FLOATS = 128 * 64;
-// the plan of a GEMM with ntile tiles on a grid of G over scratch ws (nullptr: no split); the tail is split only
-// for R == 0 with at most max_t0 tail tiles or R == 1 with at most max_t1
-P8Tail p8_tail_plan_ws(const GemmArgs& a, long ntile, long G, void* ws, long max_t0, long max_t1);
-size_t p8_slab_bytes(long G);
+// (the stream-K plan P8Tail and the tile constants W4 / W4_KT the host planner shares: ptk_internal.h)
 // the cut tail tiles' pieces summed in K order + the tile epilogue (ACT_NONE; the general epilogue's forms)
 int launch_p8_fixup(const GemmArgs& a, int act, int out, const P8Tail& tl, hipStream_t st);
 
 namespace {
-constexpr int W4 = 256;                  // output tile edge
-constexpr int W4_KT = 64;                // K granularity of the path (a pair of k-steps per barrier)
 constexpr int W4_KS = 32;                // k-step depth: one MFMA 16x16x32 deep, one ring slot
 constexpr int W4_SOPB = W4 * W4_KS * 2;  // one operand's k-step image: 256 rows x 64 B = 16 KiB
 constexpr int W4_SLOT = 2 * W4_SOPB;     // A + B per ring slot

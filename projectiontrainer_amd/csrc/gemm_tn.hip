@@ -322,79 +322,23 @@ __global__ void __launch_bounds__(512, 1) gemm_tn_kernel(GemmArgs p, uint32_t a_
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // no LDS-DMA may land after the workgroup exits
 }
 
-// the TN path takes: 16-B aligned operands with 16-B k-rows, K split into `slices` equal slices of >= 128 rows (a
-// multiple of 64), N % 64 == 0, operand extents below 4 GiB and C's below 2^31; OUT_BF16 only with the lean epilogue's form (the weight-grad
-// accumulate: bf16_linear + resid16), OUT_F32 the partials of a K split ([slices][M][ldc])
-bool tn_supported(const GemmArgs& a, int out, int slices) {
-  if (slices < 1 || a.K % (W4_KT * slices) || a.K / slices < 2 * W4_KT) return false;
-  if (a.N % 64 || a.lda % 8 || a.ldb % 8 || a.lda < a.M || a.ldb < a.N) return false;
-  if (((uintptr_t)a.A | (uintptr_t)a.B | (uintptr_t)a.C) & 15) return false;
-  if (a.amap.g || a.amap.off || a.bias || a.rowadd || a.resid || a.aux || a.aux_in || a.row_stats || a.alpha != 1.f)
-    return false;
-  // operand extents below 4 GiB less 1 MiB: 32-bit buffer offsets and num_records (the tied lm_head's dW reads the
-  // 2 GiB d(logits) [4 096][262 144]); the last tile's read past its k-row never wraps
-  const double ab = (double)a.K * a.lda * 2, bb = (double)a.K * a.ldb * 2;
-  if (ab >= 4293918720.0 || bb >= 4293918720.0) return false;
-  if (out == OUT_BF16) {
-    uint32_t cb = 0;
-    return slices == 1 && lean_epilogue_candidate(a) && lean_epilogue_ok(a, ACT_NONE, OUT_BF16, cb);
-  }
-  if (out != OUT_F32 || a.ldc % 4 || a.ldc < a.N || a.cmap.g || a.cmap.off || a.resid16 || a.bf16_linear) return false;
-  return (double)slices * a.M * a.ldc * 4 < 2147483000.0;
-}
-
-// Slice count of a weight grad (a: the OUT_BF16 accumulate form).  Cost in us: the tile rounds of the persistent
-// grid, each K / S / 64 K-tiles of ~1.15 us (a 256x256x64 step at ~75 % of one CU's MFMA rate) plus ~4 us of
-// epilogue, and for S > 1 the fp32 partials written, read back and reduced with the bf16 accumulate
-// ((8 S + 4) M N bytes at ~5 TB/s).  cfg4: dW_gate|up (54 x 5 tiles, K 14 336) 2 slices (partials capped by the
-// workspace), dW_down (5 x 27) 1, dW_qkv (6 x 5) and dW_o (5 x 4) 8
-int tn_slices(const GemmArgs& a, long part_floats) {
-  const long tiles = (long)((a.M + W4 - 1) / W4) * ((a.N + W4 - 1) / W4), cu = device_cus();
-  int best = 0;
-  double best_us = 0;
-  for (int S = 1; S <= 16; S *= 2) {
-    GemmArgs f = a;
-    int out = OUT_BF16;
-    if (S > 1) {
-      if ((double)S * a.M * a.N > (double)part_floats) break;
-      f.C = reinterpret_cast<void*>((uintptr_t)256);   // (the partials' alignment is the workspace's, checked at launch)
-      f.ldc = a.N;
-      f.bf16_linear = 0;
-      f.resid16 = nullptr;
-      f.ld_resid16 = 0;
-      out = OUT_F32;
-    }
-    if (!tn_supported(f, out, S)) continue;
-    const long rounds = (tiles * S + cu - 1) / cu;
-    const double us = (double)rounds * ((double)a.K / S / W4_KT * 1.15 + 4.0) +
-                      (S > 1 ? (8.0 * S + 4.0) * (double)a.M * a.N / 5e6 : 0.0);
-    if (!best || us < best_us) { best = S; best_us = us; }
-  }
-  return best;
-}
-
+// (what the TN path takes, its slice count and its stream-K plan -- tn_supported, tn_slices, tn_tail_plan: gemm_plan.cpp)
 size_t tn_slab_bytes() { return p8_slab_bytes(device_cus()); }
 
-// the stream-K plan of a one-slice TN GEMM over `slab` (p8_slab_bytes(CUs) bytes): any tail of at most 256 tiles
-// without a full round before it (the few-tile weight grads: dW_down 135 tiles, dW_qkv 30, dW_o 20), at most 64
-// after one (dW_gate|up: 270 = 256 + 14)
-P8Tail tn_tail_plan(const GemmArgs& a, void* slab) {
-  const long ntile = (long)((a.M + W4 - 1) / W4) * ((a.N + W4 - 1) / W4);
-  return p8_tail_plan_ws(a, ntile, device_cus(), slab, 256, 64);
-}
-
 int launch_gemm_tn(const GemmArgs& a, int out, int slices, void* slab, hipStream_t st, long k_rows) {
-  if (!tn_supported(a, out, slices)) return set_error("gemm_tn: unsupported operands (M %d N %d K %d slices %d)", a.M, a.N, a.K, slices);
+  const bool lean_epi = lean_epilogue_enabled();
+  const long ncu = device_cus();
+  if (!tn_supported(a, out, slices, lean_epi)) return set_error("gemm_tn: unsupported operands (M %d N %d K %d slices %d)", a.M, a.N, a.K, slices);
   if (k_rows < 0) k_rows = a.K;
   if (k_rows > a.K || k_rows <= a.K - W4_KT) return set_error("gemm_tn: k_rows %ld outside (K - 64, K] (K %d)", k_rows, a.K);
   const long ntile = (long)((a.M + W4 - 1) / W4) * ((a.N + W4 - 1) / W4) * slices;
-  const P8Tail tl = slices == 1 && slab ? tn_tail_plan(a, slab) : P8Tail{};
-  const long grid = tl.units ? device_cus() : std::min<long>(ntile, device_cus());
+  const P8Tail tl = slices == 1 && slab ? tn_tail_plan(a, slab, (int)ncu) : P8Tail{};
+  const long grid = tl.units ? ncu : std::min<long>(ntile, ncu);
   // num_records end at row k_rows: a K padded to a multiple of 64 reads its last rows as zero
   const uint32_t ab = (uint32_t)((double)k_rows * a.lda * 2), bb = (uint32_t)((double)k_rows * a.ldb * 2);
   uint32_t cb = 0;
   if (out == OUT_BF16) {
-    lean_epilogue_ok(a, ACT_NONE, OUT_BF16, cb);
+    lean_epilogue_ok(a, ACT_NONE, OUT_BF16, cb, lean_epi);
     if (tl.units) {
       hipLaunchKernelGGL((gemm_tn_kernel<OUT_BF16, true>), dim3((unsigned)grid), dim3(512), 0, st, a, ab, bb, cb, 1, tl);
       if (hipGetLastError() != hipSuccess) return set_error("gemm_tn launch failed");

@@ -271,95 +271,13 @@ __global__ void __launch_bounds__(256, 1) gemm_w4_kernel(GemmArgs p, uint32_t a_
 #undef W4_PIN
 }
 
-// the W4 path needs: batch 1, 16-B aligned rows of every operand it touches 8 columns at a time,
-// N % 8 == 0, byte extents of A and B below 2^31 (32-bit buffer offsets)
-bool w4_supported(const GemmArgs& a, int act, int out) {
-  if (a.N % 8 || a.K % W4_KT) return false;
-  if (a.alpha != 1.f) return false;   // the persistent epilogues take the accumulators as they are (no scale)
-  if (a.row_stats) return false;   // the softmax-statistics epilogue lives in gemm.hip's epilogue only
-  if (a.resid16 && (out != OUT_BF16 || a.ld_resid16 % 8)) return false;
-  if ((a.ldc % 8) || (a.resid && a.ld_resid % 4) || (a.rowadd && a.ld_rowadd % 4)) return false;
-  if ((a.aux || a.aux2) && a.ld_aux % 8) return false;
-  if ((a.aux_in || a.aux_in2) && a.ld_aux_in % 8) return false;
-  if (((uintptr_t)a.C | (uintptr_t)a.bias | (uintptr_t)a.resid | (uintptr_t)a.resid16 | (uintptr_t)a.rowadd | (uintptr_t)a.aux |
-       (uintptr_t)a.aux2 | (uintptr_t)a.aux_in | (uintptr_t)a.aux_in2) & 15)
-    return false;
-  if (act == ACT_GEGLU && (a.N % 32)) return false;
-  if (act == ACT_GEGLU_BWD && (!a.aux_in || !a.aux_in2 || (a.N % 16) || (a.ldc % 8))) return false;
-  if (act == ACT_GELU_ERF_BWD && !a.aux_in) return false;
-  if (out != OUT_BF16 && (act != ACT_NONE)) return false;
-  if (a.amap.g != 0) return false;   // gathered A rows: not an affine row panel
-  const double abytes = (double)(a.M + a.amap.off) * a.lda * 2, bbytes = (double)a.N * a.ldb * 2;
-  return abytes < 2147483000.0 && bbytes < 2147483000.0;
-}
-
-static int g_num_cu = 0;
-
-static int num_cu() {
-  if (!g_num_cu) {
-    int dev = 0, n = 0;
-    if (hipGetDevice(&dev) != hipSuccess ||
-        hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0)
-      n = 256;
-    g_num_cu = n;
-  }
-  return g_num_cu;
-}
-
-int device_cus() { return num_cu(); }
-
-double w4_round_fill(long M, long N) {
-  const long ntile = ((M + W4 - 1) / W4) * ((N + W4 - 1) / W4), cu = num_cu();
-  return (double)ntile / (double)(((ntile + cu - 1) / cu) * cu);
-}
-
-// the lean bf16 epilogue (gemm_persist.h w4_epilogue_lean) applies: ACT_NONE / ACT_GELU_TANH into bf16 with at most
-// a bias, the bf16-linear rounding and a bf16 residual (row-aligned with C, 16-B rows); a C row map that is an
-// offset (cmap.g == 0, or a group map without skipped rows whose group stride equals its size: the identity
-// plus cmap.off); whole 64-column wave ranges; C's extent (rows cmap.off .. M + cmap.off) below 2^31 bytes.
-// c_bytes = that extent (num_records of the store resource: rows past M are dropped).  PTK_LEAN_EPI=0 (A/B builds,
-// PTK_AB) keeps the general epilogue (bit-identical either way)
-static bool lean_on() { return PTK_AB("PTK_LEAN_EPI", 1) != 0; }
-// the lean GEGLU-backward epilogue (w4_epilogue_lean_glu): the saved g, u inputs with 16-B rows, no other epilogue
-// input, an offset C row map, whole 128-column wave ranges, extents below 2^31 bytes
-static bool lean_glu_ok(const GemmArgs& a, int act, int out, uint32_t& c_bytes) {
-  if (!lean_on() || act != ACT_GEGLU_BWD || out != OUT_BF16) return false;
-  if (a.bias || a.rowadd || a.resid || a.resid16 || a.bf16_linear || a.row_stats || a.alpha != 1.f) return false;
-  const bool affine = a.cmap.g == 0 || (a.cmap.skip == 0 && a.cmap.gs == a.cmap.g);
-  if (!affine || a.cmap.off < 0 || a.amap.g != 0 || a.N % 128 || a.ldc % 8 || ((uintptr_t)a.C & 15)) return false;
-  if (!a.aux_in || !a.aux_in2 || a.ld_aux_in % 8 || a.ld_aux_in < a.N) return false;
-  if (((uintptr_t)a.aux_in | (uintptr_t)a.aux_in2) & 15) return false;
-  if (a.ldc < 2 * a.N) return false;
-  const double side = (double)a.M * (double)a.ld_aux_in * 2.0;
-  const double bytes = ((double)a.M + (double)a.cmap.off) * (double)a.ldc * 2.0;
-  if (bytes >= 2147483000.0 || side >= 2147483000.0) return false;
-  c_bytes = (uint32_t)bytes;
-  return true;
-}
-bool lean_epilogue_ok(const GemmArgs& a, int act, int out, uint32_t& c_bytes) {
-  if (act == ACT_GEGLU_BWD) return lean_glu_ok(a, act, out, c_bytes);
-  if (!lean_on() || (act != ACT_NONE && act != ACT_GELU_TANH) || out != OUT_BF16) return false;
-  if (a.rowadd || a.resid || a.aux || a.aux2 || a.aux_in || a.aux_in2 || a.row_stats || a.alpha != 1.f) return false;
-  const bool affine = a.cmap.g == 0 || (a.cmap.skip == 0 && a.cmap.gs == a.cmap.g);
-  if (!affine || a.cmap.off < 0 || a.N % 64 || a.ldc % 8 || a.ldc < a.N || ((uintptr_t)a.C & 15)) return false;
-  if (a.bias && ((uintptr_t)a.bias & 15)) return false;
-  if (a.resid16 && (a.ld_resid16 % 8 || ((uintptr_t)a.resid16 & 15))) return false;
-  const double rows = (double)a.M + (double)a.cmap.off;
-  const double bytes = rows * (double)a.ldc * 2.0, rbytes = a.resid16 ? rows * (double)a.ld_resid16 * 2.0 : 0.0;
-  if (bytes >= 2147483000.0 || rbytes >= 2147483000.0) return false;
-  c_bytes = (uint32_t)bytes;
-  return true;
-}
-
-bool lean_epilogue_candidate(const GemmArgs& a) {
-  uint32_t cb = 0;
-  return lean_epilogue_ok(a, ACT_NONE, OUT_BF16, cb);
-}
+// (w4_supported, w4_round_fill and the lean-epilogue conditions lean_epilogue_ok: gemm_plan.cpp)
+// PTK_LEAN_EPI=0 (A/B builds, PTK_AB) keeps the general epilogue (bit-identical either way)
+bool lean_epilogue_enabled() { return PTK_AB("PTK_LEAN_EPI", 1) != 0; }
 
 int launch_gemm_w4(const GemmArgs& a, int act, int out, hipStream_t st, int max_grid) {
-  num_cu();
   const long ntile = (long)((a.M + W4 - 1) / W4) * ((a.N + W4 - 1) / W4);
-  long grid = std::min<long>(ntile, max_grid > 0 ? max_grid : g_num_cu);
+  long grid = std::min<long>(ntile, max_grid > 0 ? max_grid : device_cus());
 #ifdef PTK_P8_STAMPS
   if (const char* e = getenv("PTK_GEMM_GRID")) grid = std::min<long>(grid, atol(e));   // diagnostic: fewer CUs
 #endif
@@ -367,7 +285,7 @@ int launch_gemm_w4(const GemmArgs& a, int act, int out, hipStream_t st, int max_
   const uint32_t ab = (uint32_t)std::min<double>((double)arows * a.lda * 2, 2147483000.0);
   const uint32_t bb = (uint32_t)std::min<double>((double)a.N * a.ldb * 2, 2147483000.0);
   uint32_t cb = 0;
-  if (lean_epilogue_ok(a, act, out, cb)) {
+  if (lean_epilogue_ok(a, act, out, cb, lean_epilogue_enabled())) {
 #define PTK_W4L_CASE(ACT_)                                                                                   \
     if (act == ACT_)                                                                                         \
       hipLaunchKernelGGL((gemm_w4_kernel<ACT_, OUT_BF16, true>), dim3((unsigned)grid), dim3(256), 0, st, a, ab, bb, cb);
@@ -377,21 +295,11 @@ int launch_gemm_w4(const GemmArgs& a, int act, int out, hipStream_t st, int max_
 #undef PTK_W4L_CASE
     return hipGetLastError() == hipSuccess ? 0 : set_error("gemm_w4 launch failed");
   }
-#define PTK_W4_CASE(ACT_, OUT_)                                                                   \
-  if (act == ACT_ && out == OUT_) {                                                               \
-    hipLaunchKernelGGL((gemm_w4_kernel<ACT_, OUT_>), dim3((unsigned)grid), dim3(256), 0, st, a, ab, bb, 0u); \
-    return hipGetLastError() == hipSuccess ? 0 : set_error("gemm_w4 launch failed");              \
-  }
-  PTK_W4_CASE(ACT_NONE, OUT_BF16)
-  PTK_W4_CASE(ACT_NONE, OUT_F32)
-  PTK_W4_CASE(ACT_NONE, OUT_F32_BFR)
-  PTK_W4_CASE(ACT_GELU_TANH, OUT_BF16)
-  PTK_W4_CASE(ACT_GELU_ERF, OUT_BF16)
-  PTK_W4_CASE(ACT_GEGLU, OUT_BF16)
-  PTK_W4_CASE(ACT_GELU_ERF_BWD, OUT_BF16)
-  PTK_W4_CASE(ACT_GEGLU_BWD, OUT_BF16)
-#undef PTK_W4_CASE
-  return set_error("gemm_w4: unsupported (act=%d, out=%d)", act, out);
+  if (!gemm_act_out(act, out, [&](auto A, auto O) {
+        hipLaunchKernelGGL((gemm_w4_kernel<A(), O()>), dim3((unsigned)grid), dim3(256), 0, st, a, ab, bb, 0u);
+      }))
+    return set_error("gemm_w4: unsupported (act=%d, out=%d)", act, out);
+  return hipGetLastError() == hipSuccess ? 0 : set_error("gemm_w4 launch failed");
 }
 
 
@@ -821,60 +729,9 @@ int launch_p8_fixup(const GemmArgs& a, int act, int out, const P8Tail& tl, hipSt
   return hipGetLastError() == hipSuccess ? 0 : set_error("p8 fixup launch failed");
 }
 
-// the p8 path takes what the w4 path takes, at K >= 128 (a tile's first and last k-step pairs are peeled)
-bool p8_supported(const GemmArgs& a, int act, int out) { return a.K >= 128 && w4_supported(a, act, out); }
-
-// stream-K tail scratch (P8Tail): the arrival counters first (zeroed by p8_tail_scratch_zero at the start of
-// every model-level call that uses it; each launch leaves them zero), then the partial slabs
-constexpr size_t P8_CNT_BYTES = 16384;
-size_t p8_tail_scratch_bytes() {
-  num_cu();
-  return P8_CNT_BYTES + (size_t)g_num_cu * 2 * 8 * P8_WAVE_FLOATS * sizeof(float);
-}
-
-// the stream-K plan of a launch.  Cost model of the tail round, in K-tiles of one workgroup (a 256x256x64 step,
-// ~1.3 us): unsplit, nt; split over Gs workgroups, ceil(U / Gs) plus the partial writes of a workgroup's (at most
-// two) cut pieces (a 256-KiB slab each, ~1 K-tile) and the fixup launch (~5 K-tiles).  The cheapest Gs is taken
-// when it saves >= 10 % of the round.
-size_t p8_slab_bytes(long G) { return (size_t)G * 2 * 8 * P8_WAVE_FLOATS * sizeof(float); }
-P8Tail p8_tail_plan_ws(const GemmArgs& a, long ntile, long G, void* slab, long max_t0, long max_t1) {
-  P8Tail tl;
-  const long R = ntile / G, T = ntile - R * G, nt = a.K / W4_KT;
-  if (!slab || T == 0 || (nt & 1)) return tl;
-  if (!((R == 0 && T <= max_t0) || (R == 1 && T <= max_t1))) return tl;
-  const long U = T * (nt / 2);                                // tail units: pairs of K-tiles
-  double best = (double)nt * 0.9;
-  long bestG = 0;
-  for (long gs = T + 1; gs <= G; ++gs) {
-    const long per = (U + gs - 1) / gs;                       // units of the busiest workgroup
-    if (U / gs < 1) break;                                    // (every workgroup >= 1 unit)
-    const double cost = 2.0 * (double)per + 2.0 + 5.0;
-    if (cost < best - 1e-9) { best = cost; bestG = gs; }
-  }
-  if (!bestG || R + 3 > 64 || G > 1023 || ntile > 65535) return tl;   // the kernel's per-lane segment table
-  tl.dp_tiles = (int)(R * G);
-  tl.units = (int)U;
-  tl.gsplit = (int)bestG;
-  tl.slab = (float*)slab;
-  return tl;
-}
-
-// the 8-wave kernel's plan: the scratch of the descriptor or the model-level scope (slabs after the counters).
-// Long K only (K >= 4096: the fixup launch and the partial writes cost a few K-tiles), and a tail the split
-// shortens without losing the lock-step L2 sharing of a round: a grid of at most 64 tiles, or one full round plus
-// at most 128.  Measured (tools/sk_ab.py, r05, same box): SigLIP fc2 0.90x, projector fc2 0.91x, Stage 2's
-// down / d(gate|up) dX 0.72 / 0.63x, projector dW1 (160 tiles, no full round) 0.90x; slower where many tiles
-// share no full round (projector dW2 200 tiles 1.31x, the Stage-2 SigLIP fc2 144 tiles 1.11x, Gemma's 440-tile
-// projections with 184 tail tiles 1.06-1.08x)
-static P8Tail p8_tail_plan(const GemmArgs& a, long ntile, long G, int act, int out) {
-  void* ws = a.tail_ws ? a.tail_ws : tail_scope();
-  if (!ws || act != ACT_NONE || (out != OUT_BF16 && out != OUT_F32 && out != OUT_F32_BFR)) return P8Tail{};
-  if (a.K < 4096) return P8Tail{};
-#ifndef PTK_SK_MAXT1
-#define PTK_SK_MAXT1 128   // A/B builds (make ablib AB_DEFS=-DPTK_SK_MAXT1=..) vary the one-round-plus-tail limit
-#endif
-  return p8_tail_plan_ws(a, ntile, G, (char*)ws + P8_CNT_BYTES, 64, PTK_SK_MAXT1);
-}
+// stream-K tail scratch (P8Tail): the arrival counters first (P8_CNT_BYTES), then the partial slabs; the plan over
+// it: gemm_plan.cpp p8_tail_plan
+size_t p8_tail_scratch_bytes() { return P8_CNT_BYTES + p8_slab_bytes(device_cus()); }
 
 // The model-level calls lend their tail scratch to every GEMM they launch (PTK_STREAMK=0 in an A/B build, PTK_AB:
 // never, the default dispatch without the tail; r04's opt-in predates the parallel fixup)
@@ -892,18 +749,11 @@ TailScratchScope::~TailScratchScope() { g_tail_scope = prev; }
 // the model-level workspaces reserve tail scratch when it will be lent
 size_t p8_tail_scratch_bytes_models() { return streamk_models() ? p8_tail_scratch_bytes() : 0; }
 
-int p8_tail_split(const GemmArgs& a, int act, int out) {
-  num_cu();
-  const long ntile = (long)((a.M + W4 - 1) / W4) * ((a.N + W4 - 1) / W4);
-  return p8_tail_plan(a, ntile, g_num_cu, act, out).gsplit;
-}
-
 // K-sliced plain fp32 GEMM on the 8-wave kernel (P8Tail::zslices): C[z][M][N] = A[:, zK:(z+1)K] B[:, zK:(z+1)K]^T
 // for z < slices, a.K the slice depth; the slices run as S x M rows of persistent tiles in lock-step rounds
 // (every slice's tiles share their operand panels through L2), the caller sums the partials.  Plain fp32 out,
 // M % 256 == 0 (no tile straddles two slices), byte offsets within 4 GiB.
 int launch_gemm_p8_kslices(const GemmArgs& a, int slices, hipStream_t st) {
-  num_cu();
   if (slices < 1 || a.M % W4 || a.K < 128 || a.K % W4_KT || a.cmap.g || a.cmap.off || a.amap.g || a.amap.off ||
       a.bias || a.rowadd || a.resid || a.resid16 || a.aux || a.row_stats)
     return set_error("gemm_p8_kslices: unsupported operands");
@@ -915,7 +765,7 @@ int launch_gemm_p8_kslices(const GemmArgs& a, int slices, hipStream_t st) {
   P8Tail tl;
   tl.zslices = slices;
   const long ntile = (long)(g.M / W4) * ((g.N + W4 - 1) / W4);
-  const long grid = std::min<long>(ntile, g_num_cu);
+  const long grid = std::min<long>(ntile, device_cus());
   const uint32_t ab = (uint32_t)std::min<double>((double)a.M * a.lda * 2, 4294967040.0);
   const uint32_t bb = (uint32_t)std::min<double>((double)a.N * a.ldb * 2, 4294967040.0);
   hipLaunchKernelGGL((gemm_p8_kernel<ACT_NONE, OUT_F32, false>), dim3((unsigned)grid), dim3(512), 0, st, g, ab, bb, tl,
@@ -923,35 +773,13 @@ int launch_gemm_p8_kslices(const GemmArgs& a, int slices, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? 0 : set_error("gemm_p8_kslices launch failed");
 }
 
-// the tile height of a plain / GELU-tanh 8-wave GEMM without a stream-K tail: the TM of {256, 224, 192, 160} with the
-// lowest tile rounds x (TM + 128), a tie with 256 rows going to the shorter tile (SigLIP fc1: 6 rounds of 192 = 5 of
-// 256; +0.15 % on the cfg2 step over three same-box alternations, profiles/r05_tm160_ab.txt; with a 5 % margin it
-// stayed at 256).  The 128 rows' worth per round is what shorter tiles do not shed (prologue, epilogue, the DMA / LDS work per MFMA): fitted to tools/p8_probe.py
-// (r05, same box): Gemma o 59.6 / 54.1 / 68.5 us at 256 / 224 / 192 rows, dO 65.8 / 59.5 / 54.4, q|k|v 90.7 / 88.0
-// / 81.4, down 340 / 312 / 407, SigLIP fc1 149 / 157 / 153 (on another box 154.7 at 256, 148.1 at 192); 160 rows:
-// SigLIP o 52.1 -> 46.4 us (2 rounds of 160 vs 2 of 192), Gemma dO stays at 192 (57.6 vs 70.9), profiles/r05_tm160_ab.txt
-int p8_tile_height(const GemmArgs& a, int act, int out) {
-  num_cu();
-  if (!(act == ACT_NONE || (act == ACT_GELU_TANH && out == OUT_BF16))) return 256;
-  const long nbn = (a.N + W4 - 1) / W4, cu = g_num_cu;
-  auto cost = [&](long tm) { return (double)((((a.M + tm - 1) / tm) * nbn + cu - 1) / cu) * (double)(tm + 128); };
-  const double c256 = cost(256);
-  int best = 256;
-  double bc = c256;
-  for (int tm : {224, 192, 160}) {
-    const double c = cost(tm);
-    if (c < bc || (c == bc && best == 256)) { bc = c; best = tm; }   // a tie with 256 rows goes to the shorter tile
-  }
-  return best;
-}
-
 template <int TM>
-static int launch_p8_short(const GemmArgs& a, int act, int out, hipStream_t st, long grid) {
+static int launch_p8_short(const GemmArgs& a, int act, int out, hipStream_t st, long grid, bool lean_epi) {
   const uint32_t ab = (uint32_t)std::min<double>((double)(a.M + a.amap.off) * a.lda * 2, 2147483000.0);
   const uint32_t bb = (uint32_t)std::min<double>((double)a.N * a.ldb * 2, 2147483000.0);
   const P8Tail tl{};
   uint32_t cb = 0;
-  if (lean_epilogue_ok(a, act, out, cb)) {
+  if (lean_epilogue_ok(a, act, out, cb, lean_epi)) {
     if (act == ACT_NONE)
       hipLaunchKernelGGL((gemm_p8_kernel<ACT_NONE, OUT_BF16, false, true, TM>), dim3((unsigned)grid), dim3(512), 0,
                          st, a, ab, bb, tl, cb);
@@ -974,22 +802,23 @@ static int launch_p8_short(const GemmArgs& a, int act, int out, hipStream_t st, 
   return hipGetLastError() == hipSuccess ? 0 : set_error("gemm_p8 launch failed");
 }
 
-int launch_gemm_p8(const GemmArgs& a, int act, int out, hipStream_t st, bool sk, int tm) {
-  num_cu();
-  if (tm != 256 && !sk) {
+// tl: the plan's stream-K tail (gemm_plan: units == 0 none; the census counts a launch with one as p8sk), tm: the
+// plan's tile rows
+int launch_gemm_p8(const GemmArgs& a, int act, int out, hipStream_t st, const P8Tail& tl, int tm) {
+  const long ncu = device_cus();
+  const bool lean_epi = lean_epilogue_enabled();
+  if (tm != 256 && !tl.units) {
     if (!(act == ACT_NONE || (act == ACT_GELU_TANH && out == OUT_BF16)))
       return set_error("gemm_p8: %d-row tiles take the plain / GELU-tanh epilogues only", tm);
     if (tm != 224 && tm != 192 && tm != 160) return set_error("gemm_p8: tile height %d (256, 224, 192, 160)", tm);
     const long ntm = (long)((a.M + tm - 1) / tm) * ((a.N + W4 - 1) / W4);
-    const long grid = std::min<long>(ntm, g_num_cu);
-    if (tm == 224) return launch_p8_short<224>(a, act, out, st, grid);
-    if (tm == 192) return launch_p8_short<192>(a, act, out, st, grid);
-    return launch_p8_short<160>(a, act, out, st, grid);
+    const long grid = std::min<long>(ntm, ncu);
+    if (tm == 224) return launch_p8_short<224>(a, act, out, st, grid, lean_epi);
+    if (tm == 192) return launch_p8_short<192>(a, act, out, st, grid, lean_epi);
+    return launch_p8_short<160>(a, act, out, st, grid, lean_epi);
   }
   const long ntile = (long)((a.M + W4 - 1) / W4) * ((a.N + W4 - 1) / W4);
-  // the stream-K plan only where launch_gemm's gates chose the tail split (its census counts it as p8sk)
-  const P8Tail tl = sk ? p8_tail_plan(a, ntile, g_num_cu, act, out) : P8Tail{};
-  long grid = tl.units ? g_num_cu : std::min<long>(ntile, g_num_cu);
+  long grid = tl.units ? ncu : std::min<long>(ntile, ncu);
 #ifdef PTK_P8_STAMPS
   if (const char* e = getenv("PTK_GEMM_GRID")) grid = std::min<long>(grid, atol(e));   // diagnostic: fewer CUs
 #endif
@@ -997,7 +826,22 @@ int launch_gemm_p8(const GemmArgs& a, int act, int out, hipStream_t st, bool sk,
   const uint32_t ab = (uint32_t)std::min<double>((double)arows * a.lda * 2, 2147483000.0);
   const uint32_t bb = (uint32_t)std::min<double>((double)a.N * a.ldb * 2, 2147483000.0);
   uint32_t cb = 0;
-  if (!tl.units && lean_epilogue_ok(a, act, out, cb)) {
+  if (tl.units) {
+    if (act != ACT_NONE) return set_error("gemm_p8: the stream-K tail takes ACT_NONE only (act=%d)", act);
+    if (lean_epilogue_ok(a, act, out, cb, lean_epi)) {   // whole tiles take the lean epilogue
+      hipLaunchKernelGGL((gemm_p8_kernel<ACT_NONE, OUT_BF16, true, true>), dim3((unsigned)grid), dim3(512), 0, st, a,
+                         ab, bb, tl, cb);
+    } else if (!gemm_act_out(act, out, [&](auto A, auto O) {
+                 if constexpr (A() == ACT_NONE)   // (the tail kernel is instantiated for the plain epilogues only)
+                   hipLaunchKernelGGL((gemm_p8_kernel<ACT_NONE, O(), true>), dim3((unsigned)grid), dim3(512), 0, st, a,
+                                      ab, bb, tl, 0u);
+               })) {
+      return set_error("gemm_p8: unsupported (act=%d, out=%d)", act, out);
+    }
+    if (hipGetLastError() != hipSuccess) return set_error("gemm_p8 launch failed");
+    return launch_p8_fixup(a, act, out, tl, st);
+  }
+  if (lean_epilogue_ok(a, act, out, cb, lean_epi)) {
 #define PTK_P8L_CASE(ACT_)                                                                                   \
     if (act == ACT_)                                                                                         \
       hipLaunchKernelGGL((gemm_p8_kernel<ACT_, OUT_BF16, false, true>), dim3((unsigned)grid), dim3(512), 0, st, a, ab, \
@@ -1008,39 +852,11 @@ int launch_gemm_p8(const GemmArgs& a, int act, int out, hipStream_t st, bool sk,
 #undef PTK_P8L_CASE
     return hipGetLastError() == hipSuccess ? 0 : set_error("gemm_p8 launch failed");
   }
-#define PTK_P8_CASE(ACT_, OUT_)                                                                       \
-  if (act == ACT_ && out == OUT_) {                                                                   \
-    hipLaunchKernelGGL((gemm_p8_kernel<ACT_, OUT_, false>), dim3((unsigned)grid), dim3(512), 0, st, a, ab, bb, tl, 0u); \
-    return hipGetLastError() == hipSuccess ? 0 : set_error("gemm_p8 launch failed");                  \
-  }
-#define PTK_P8SK_CASE(ACT_, OUT_)                                                                     \
-  if (act == ACT_ && out == OUT_) {                                                                   \
-    hipLaunchKernelGGL((gemm_p8_kernel<ACT_, OUT_, true>), dim3((unsigned)grid), dim3(512), 0, st, a, ab, bb, tl, 0u); \
-    if (hipGetLastError() != hipSuccess) return set_error("gemm_p8 launch failed");                  \
-    return launch_p8_fixup(a, act, out, tl, st);                                                      \
-  }
-  if (tl.units) {
-    if (act == ACT_NONE && lean_epilogue_ok(a, act, out, cb)) {   // whole tiles take the lean epilogue
-      hipLaunchKernelGGL((gemm_p8_kernel<ACT_NONE, OUT_BF16, true, true>), dim3((unsigned)grid), dim3(512), 0, st, a,
-                         ab, bb, tl, cb);
-      if (hipGetLastError() != hipSuccess) return set_error("gemm_p8 launch failed");
-      return launch_p8_fixup(a, act, out, tl, st);
-    }
-    PTK_P8SK_CASE(ACT_NONE, OUT_BF16)
-    PTK_P8SK_CASE(ACT_NONE, OUT_F32)
-    PTK_P8SK_CASE(ACT_NONE, OUT_F32_BFR)
-  }
-  PTK_P8_CASE(ACT_NONE, OUT_BF16)
-  PTK_P8_CASE(ACT_NONE, OUT_F32)
-  PTK_P8_CASE(ACT_NONE, OUT_F32_BFR)
-  PTK_P8_CASE(ACT_GELU_TANH, OUT_BF16)
-  PTK_P8_CASE(ACT_GELU_ERF, OUT_BF16)
-  PTK_P8_CASE(ACT_GEGLU, OUT_BF16)
-  PTK_P8_CASE(ACT_GELU_ERF_BWD, OUT_BF16)
-  PTK_P8_CASE(ACT_GEGLU_BWD, OUT_BF16)
-#undef PTK_P8_CASE
-#undef PTK_P8SK_CASE
-  return set_error("gemm_p8: unsupported (act=%d, out=%d)", act, out);
+  if (!gemm_act_out(act, out, [&](auto A, auto O) {
+        hipLaunchKernelGGL((gemm_p8_kernel<A(), O(), false>), dim3((unsigned)grid), dim3(512), 0, st, a, ab, bb, tl, 0u);
+      }))
+    return set_error("gemm_p8: unsupported (act=%d, out=%d)", act, out);
+  return hipGetLastError() == hipSuccess ? 0 : set_error("gemm_p8 launch failed");
 }
 
 }  // namespace ptk

@@ -271,50 +271,23 @@ GemmaWs gemma_layout(Bump& bp, const ptk_gemma3_config* c, int B, int T, int Sp,
   return w;
 }
 
-// Split-K for long-K GEMMs whose 256x256 tile grid fills few of the CUs' rounds (measured, tools/splitk_probe.py
-// r02: the cfg4 shapes dW_qkv 313 -> 73 us and dW_o 313 -> 68 us at 4 slices; dW_down, dW_gate|up, the
-// d(gate|up) dX and the down projection at 280 tiles -8..-16 % at 2 slices; the cfg2 d(gate|up) dX at 440
-// tiles is slower split, the vocab-wide lm_head dW too).  ACT_NONE only; OUT_F32, or OUT_BF16 with the
-// optional bf16 accumulate (bf16_linear + resid16, the weight-grad epilogue).  The slices go to the batched
-// 128x128 kernel as fp32 partials [S][M][N]; one pass sums them in slice order (deterministic).
+// Split-K for long-K GEMMs whose 256x256 tile grid fills few of the CUs' rounds: the rule is gemm_plan.cpp's
+// gemm_split_plan, here are its launches.  ACT_NONE only; OUT_F32, or OUT_BF16 with the optional bf16 accumulate
+// (bf16_linear + resid16, the weight-grad epilogue).  The slices go to the batched 128x128 kernel as fp32 partials
+// [S][M][N]; one pass sums them in slice order (deterministic).
 int gemm_split(const GemmArgs& a, int out, float* part, long part_floats, hipStream_t st) {
-  // the persistent kernel's stream-K tail takes the shapes it measured faster on (gemm_w4.hip p8_tail_plan:
-  // Stage 2's weight grads and M = 14 336 projections) before any host-side split
-  if (a.M >= 1024 && a.N >= 256 && a.N <= 16384 && p8_supported(a, ACT_NONE, out) && p8_tail_split(a, ACT_NONE, out))
-    return launch_gemm(a, ACT_NONE, out, 1, st);
-  // long-K GEMMs whose 256x256 tiles leave a thin last round (Stage 2's d(gate|up) dX and down projection at M =
-  // 14 336: 280 tiles = 256 + 24): the 8-wave kernel's stream-K tail over the split-K scratch, its pieces summed by
-  // p8_fixup_kernel (r05, tools/sk_ab.py same box: 419 / 216 us vs 662 / 298 unsplit; the 2-slice 128x128 split
-  // below ran them at ~390 + 26 us on average)
-  if (streamk_enabled() && a.K >= 4096 && part && (size_t)part_floats * sizeof(float) >= p8_tail_scratch_bytes() &&
-      a.M >= 1024 && a.N >= 256 && a.N <= 16384) {
+  const GemmPlanEnv env = gemm_plan_env();
+  const GemmSplitPlan sp = gemm_split_plan(a, out, part ? part_floats : 0, env);
+  if (sp.kc == 0) {   // unsplit: launched with the plan the decision was made on (a force mode plans again at the launch)
     GemmArgs b = a;
-    b.tail_ws = part;
-    if (p8_supported(b, ACT_NONE, out) && p8_tail_split(b, ACT_NONE, out)) return launch_gemm(b, ACT_NONE, out, 1, st);
+    GemmPlan plan = sp.direct;
+    if (sp.tail_ws) {   // the split-K scratch as the stream-K tail's
+      b.tail_ws = part;
+      plan.tail.slab = reinterpret_cast<float*>(reinterpret_cast<char*>(part) + P8_CNT_BYTES);
+    }
+    return launch_gemm(b, ACT_NONE, out, 1, st, env.force_tiles == 0 ? &plan : nullptr);
   }
-  // one partial round of 256x256 tiles: the 8-wave kernel unsplit (launch_gemm's single-round rule) beats the
-  // split-K 128x128 slices (Stage 2 at bs 8: the down projection 133.6 vs 177.8 us); K <= 8192 as launch_gemm's own
-  // single-round rule, so a longer K (Gemma3-4B's down projection, K 10 240) keeps the split
-  if (a.M >= 4096 && a.K <= 8192 && (long)((a.M + 255) / 256) * ((a.N + 255) / 256) <= device_cus() && out == OUT_BF16 &&
-      p8_supported(a, ACT_NONE, out) && lean_epilogue_candidate(a))
-    return launch_gemm(a, ACT_NONE, out, 1, st);
-  const long nbig = (long)((a.M + 255) / 256) * ((a.N + 255) / 256);
-  int S = 1, kmin = 1024;
-  if (a.K >= 4096 && nbig <= 64) S = 4;
-  else if (a.K >= 4096 && nbig <= 300) S = 2;
-  // small M (cfg1, bs 2: M = 520): the 128x128 tile grid alone leaves most CUs idle, so split K until
-  // the slices fill about two blocks per CU (slices >= 256 deep)
-  const long n128 = (long)((a.M + 127) / 128) * ((a.N + 127) / 128), cus = device_cus();
-  if (n128 * 2 <= cus) {
-    kmin = 256;
-    while (n128 * S * 2 <= 2 * cus && a.K / (S * 2) >= kmin) S *= 2;
-  }
-  while (S > 1 && ((long)S * a.M * a.N > part_floats || a.K / S < kmin || a.N % 4 || a.ldc % 4)) S /= 2;
-  const bool plain = !a.rowadd && !a.resid && !a.aux && !a.aux_in && a.amap.g == 0 && a.amap.off == 0 &&
-                     a.cmap.g == 0 && a.cmap.off == 0 && a.bias == nullptr && a.alpha == 1.f;
-  if (S == 1 || !plain || !part) return launch_gemm(a, ACT_NONE, out, 1, st);
-  const int kc = (a.K / S + 63) / 64 * 64;
-  const int nfull = a.K / kc, rem = a.K - nfull * kc;
+  const int kc = sp.kc, nfull = sp.slices, rem = sp.rem;
   GemmArgs b = a;
   b.C = part; b.ldc = a.N; b.K = kc;
   b.sA0 = kc; b.sB0 = kc; b.sC0 = (long)a.M * a.N;
@@ -355,11 +328,12 @@ int weight_grad(const bf16_t* dy, long lddy, RowMap ymap, int Ny, const bf16_t* 
     g.bf16_linear = 1;
     g.resid16 = (const bf16_t*)grad;
     g.ld_resid16 = Nx;
+    const GemmPlanEnv env = gemm_plan_env();
     // with a slab for the stream-K tail (the fp32 scratch): one slice, the tail round's K-tiles spread over the
     // CUs; otherwise equal K slices summed by splitk_reduce
-    if (skpart && (size_t)sk_floats * sizeof(float) >= tn_slab_bytes() && tn_supported(g, OUT_BF16, 1))
+    if (skpart && (size_t)sk_floats * sizeof(float) >= tn_slab_bytes() && tn_supported(g, OUT_BF16, 1, env.lean_epi))
       return gemm_tn(g, OUT_BF16, 1, skpart, st, rows);
-    const int S = skpart ? tn_slices(g, sk_floats) : (tn_supported(g, OUT_BF16, 1) ? 1 : 0);
+    const int S = skpart ? tn_slices(g, sk_floats, env) : (tn_supported(g, OUT_BF16, 1, env.lean_epi) ? 1 : 0);
     if (S == 1) return gemm_tn(g, OUT_BF16, 1, nullptr, st, rows);
     if (S > 1) {
       GemmArgs b = g;

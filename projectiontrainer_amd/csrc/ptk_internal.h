@@ -4,6 +4,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "common.h"
 
 namespace ptk {
@@ -67,47 +69,123 @@ struct GemmArgs {
   void* tail_ws = nullptr;
 };
 
-int launch_gemm(const GemmArgs& a, int act, int out, int batch, hipStream_t st);
 // kernel families launch_gemm dispatches to (census: path_counts, ptk_gemm_path_counts)
 enum GemmPath { GEMM_PATH_NT = 0, GEMM_PATH_BIG = 1, GEMM_PATH_BIG2 = 2, GEMM_PATH_W4 = 3, GEMM_PATH_NTB = 4,
                 GEMM_PATH_P8SK = 5, GEMM_PATH_P8 = 6, GEMM_PATH_TN = 7, GEMM_NPATH = 9 };   // (8: unused since r06)
 int path_counts(int64_t* out, int reset);   // out [GEMM_NPATH][8] launches per (path, act class)
+int device_cus();   // compute units of the current device (capi.cpp: the one cache; 256 when no device answers)
+
+// the (act, out) pairs every GEMM tile family instantiates, as template arguments: f(integral_constant<int, ACT>,
+// integral_constant<int, OUT>) runs for the matching pair; false when the pair has no kernel
+template <class F>
+inline bool gemm_act_out(int act, int out, F&& f) {
+#define PTK_ACT_OUT(ACT_, OUT_)                                                          \
+  if (act == ACT_ && out == OUT_) {                                                      \
+    f(std::integral_constant<int, ACT_>{}, std::integral_constant<int, OUT_>{});         \
+    return true;                                                                         \
+  }
+  PTK_ACT_OUT(ACT_NONE, OUT_BF16)
+  PTK_ACT_OUT(ACT_NONE, OUT_F32)
+  PTK_ACT_OUT(ACT_NONE, OUT_F32_BFR)
+  PTK_ACT_OUT(ACT_GELU_TANH, OUT_BF16)
+  PTK_ACT_OUT(ACT_GELU_ERF, OUT_BF16)
+  PTK_ACT_OUT(ACT_GEGLU, OUT_BF16)
+  PTK_ACT_OUT(ACT_GELU_ERF_BWD, OUT_BF16)
+  PTK_ACT_OUT(ACT_GEGLU_BWD, OUT_BF16)
+#undef PTK_ACT_OUT
+  return false;
+}
+
+// ---- GEMM dispatch planner (gemm_plan.cpp): the only place a GEMM shape rule lives.  Pure host functions of the
+// operands and a GemmPlanEnv: no kernels, no HIP calls, no environment reads, no globals ----
+constexpr int W4 = 256;     // output tile edge of the persistent kernels (gemm_w4.hip, gemm_tn.hip)
+constexpr int W4_KT = 64;   // K granularity of those paths (a pair of k-steps per barrier)
+// stream-K tail of the persistent 8-wave kernels (gemm_w4.hip gemm_p8_kernel, gemm_tn.hip gemm_tn_kernel): the
+// plan (p8_tail_plan) and the fixup that sums the cut tiles' pieces (launch_p8_fixup), described in gemm_w4.hip
+struct P8Tail {
+  int dp_tiles = 0;           // tiles [0, dp_tiles) run whole (R rounds of G)
+  int units = 0;              // U = tail tiles x K-tile pairs (0: no tail split)
+  int gsplit = 0;             // Gs: workgroups sharing the tail
+  float* slab = nullptr;      // [G][2 slots][8 waves][128 x 64] fp32 partials
+  // K slices as extra row tiles (no tail split): the grid's M = zslices x the real M; virtual row tile bm covers
+  // real rows (bm % (nbm / zslices)) x 256 and K rows [z K, (z + 1) K) of the operands (z = bm / (nbm / zslices)),
+  // so slice z's fp32 partial lands at output rows z M_real .. (gemm_p8_kslices)
+  int zslices = 1;
+};
+constexpr size_t P8_WAVE_FLOATS = 128 * 64;
+// stream-K tail scratch: the arrival counters first (unused since the fixup kernel), then the partial slabs
+constexpr size_t P8_CNT_BYTES = 16384;
+// what the rule may depend on besides the operands: launch_gemm fills it with gemm_plan_env() (gemm.hip)
+struct GemmPlanEnv {
+  int ncu = 256;               // compute units of the device
+  int force_tiles = 0;         // the test force mode (ptk_gemm_force_small_tiles)
+  bool p8_all = false;         // A/B switch PTK_P8=1: every w4 shape on the 8-wave kernel
+  bool tm_short = true;        // A/B switch PTK_TM224: 224- / 192- / 160-row tiles where they undercut 256 rows
+  bool lean_epi = true;        // A/B switch PTK_LEAN_EPI: the lean bf16 epilogues
+  bool streamk = true;         // A/B switch PTK_STREAMK: gemm_split may lend its split-K scratch to the tail
+  void* tail_scope = nullptr;  // tail scratch lent by the model-level call (TailScratchScope), if any
+};
+GemmPlanEnv gemm_plan_env();
+struct GemmPlan {
+  int path = GEMM_PATH_NT;     // GEMM_PATH_*
+  int tm = 256;                // tile rows: 256 / 224 / 192 / 160 (p8 only)
+  P8Tail tail;                 // the stream-K plan, computed once (units == 0: none)
+  bool single_round = false;   // the single-round predicate chose the 8-wave kernel (gemm_split_plan: no K split)
+};
+GemmPlan gemm_plan(const GemmArgs& a, int act, int out, int batch, const GemmPlanEnv& env);
+// validate, plan (or take `planned`, a plan gemm_plan made for these operands under the current env), launch
+int launch_gemm(const GemmArgs& a, int act, int out, int batch, hipStream_t st, const GemmPlan* planned = nullptr);
+// gemm_split's decision (models.cpp launches it).  kc == 0: launch_gemm directly (tail_ws: with the split-K scratch
+// as the descriptor's tail scratch); kc != 0: a K split into `slices` full slices of depth kc (one batched launch;
+// slices may be 1 when the K-tile count is odd) plus one slice of depth rem when rem != 0, as fp32 partials
+struct GemmSplitPlan {
+  int slices = 1, kc = 0, rem = 0;
+  bool tail_ws = false;
+  GemmPlan direct;   // kc == 0: the unsplit launch's plan under force mode 0 (tail_ws: its slab is the caller's to set)
+};
+GemmSplitPlan gemm_split_plan(const GemmArgs& a, int out, long part_floats, const GemmPlanEnv& env);
 // persistent 256x256 4-wave GEMM (gemm_w4.hip): batch 1 only; w4_supported says whether a shape qualifies
 bool w4_supported(const GemmArgs& a, int act, int out);
 int launch_gemm_w4(const GemmArgs& a, int act, int out, hipStream_t st, int max_grid);
 // fraction of the persistent grid's tile rounds that hold work: ntile / (ceil(ntile / CUs) * CUs)
-double w4_round_fill(long M, long N);
-int device_cus();   // compute units of the current device (cached)
-// persistent 8-wave variant (gemm_w4.hip): the w4 tiles and ring with two waves per SIMD
+double w4_round_fill(long M, long N, int ncu);
+// persistent 8-wave variant (gemm_w4.hip): the w4 tiles and ring with two waves per SIMD; tail: the plan's stream-K
+// tail (units == 0: none), tm: the plan's tile rows
 bool p8_supported(const GemmArgs& a, int act, int out);
-int launch_gemm_p8(const GemmArgs& a, int act, int out, hipStream_t st, bool sk, int tm = 256);
-int p8_tile_height(const GemmArgs& a, int act, int out);   // 256, or 224 / 192 where shorter tiles fill the rounds
+int launch_gemm_p8(const GemmArgs& a, int act, int out, hipStream_t st, const P8Tail& tail, int tm = 256);
+int p8_tile_height(const GemmArgs& a, int act, int out, int ncu);   // 256, or 224 / 192 / 160 where shorter tiles fill the rounds
 int launch_gemm_p8_kslices(const GemmArgs& a, int slices, hipStream_t st);   // K slices as row tiles (fp32 partials)
 int gemm_p8_kslices(const GemmArgs& a, int slices, hipStream_t st);          // + census / timers (gemm.hip)
-// the persistent kernels would take their lean bf16 epilogue for this plain bf16 GEMM (gemm_w4.hip lean_epilogue_ok)
-bool lean_epilogue_candidate(const GemmArgs& a);
-bool lean_epilogue_ok(const GemmArgs& a, int act, int out, uint32_t& c_bytes);   // + c_bytes: C's extent (store rsrc)
+// the persistent kernels would take their lean bf16 epilogue for this plain bf16 GEMM (lean_epilogue_ok)
+bool lean_epilogue_candidate(const GemmArgs& a, bool lean_epi);
+bool lean_epilogue_ok(const GemmArgs& a, int act, int out, uint32_t& c_bytes, bool lean_epi);   // + c_bytes: C's extent (store rsrc)
+bool lean_epilogue_enabled();   // the A/B switch PTK_LEAN_EPI (gemm_w4.hip; the product library: on)
 // persistent TN GEMM (gemm_tn.hip): C[M,N] = A[K,M]^T B[K,N] on the token-major operands of a weight grad, lda / ldb
 // their row strides.  OUT_BF16: slices == 1 and the weight-grad accumulate (bf16_linear + resid16 == C), with the
 // stream-K tail of the 8-wave kernel when `slab` (tn_slab_bytes() bytes) is given and the plan splits; OUT_F32:
 // fp32 partials of `slices` equal K slices at C + z M ldc.  tn_slices: the slice count the cost model picks for
 // the weight-grad form without a slab (partials within part_floats), 0 when the TN path does not take the shape.
 // gemm_tn (gemm.hip) launches with the census (GEMM_PATH_TN) and live timers
-bool tn_supported(const GemmArgs& a, int out, int slices);
-int tn_slices(const GemmArgs& a, long part_floats);
+bool tn_supported(const GemmArgs& a, int out, int slices, bool lean_epi);
+int tn_slices(const GemmArgs& a, long part_floats, const GemmPlanEnv& env);
+P8Tail tn_tail_plan(const GemmArgs& a, void* slab, int ncu);
 size_t tn_slab_bytes();
 // k_rows (>= 0): the operands' real row count when K is padded up to a multiple of 64 (rows k_rows .. K - 1 are
 // past the buffer ranges and read as zero)
 int launch_gemm_tn(const GemmArgs& a, int out, int slices, void* slab, hipStream_t st, long k_rows = -1);
 int gemm_tn(const GemmArgs& a, int out, int slices, void* slab, hipStream_t st, long k_rows = -1);
 int wgrad_tn_enabled();   // the TN weight-grad path is on (models.cpp; A/B switch PTK_WGRAD_TN)
-// stream-K tail of the persistent 8-wave kernel: scratch bytes (arrival counters, then partial slabs), the
-// workgroups its plan spreads a GEMM's tail over (0: no split), and the thread-local scratch a model-level
-// call lends to every GEMM it launches (the counters are zeroed when the scope opens)
+// stream-K tail of the persistent 8-wave kernel: scratch bytes (arrival counters, then partial slabs), the plan of
+// a GEMM with ntile tiles on a grid of G over slabs `slab` (nullptr: no split; the tail is split only for R == 0
+// with at most max_t0 tail tiles or R == 1 with at most max_t1), the 8-wave kernel's plan over the scratch of the
+// descriptor or the model-level scope (without launch_gemm's M / N / batch gates: ptk_gemm_tail_split), and the
+// thread-local scratch a model-level call lends to every GEMM it launches
 size_t p8_tail_scratch_bytes();
 size_t p8_tail_scratch_bytes_models();   // 0 when the A/B build turns the tail off (PTK_STREAMK=0)
+size_t p8_slab_bytes(long G);
 bool streamk_enabled();                  // the stream-K tail is on (the product library: always)
-int p8_tail_split(const GemmArgs& a, int act, int out);
+P8Tail p8_tail_plan_ws(const GemmArgs& a, long ntile, long G, void* slab, long max_t0, long max_t1);
+P8Tail p8_tail_plan(const GemmArgs& a, int act, int out, const GemmPlanEnv& env);
 void* tail_scope();
 struct TailScratchScope {
   void* prev;
