@@ -86,8 +86,18 @@ typedef struct {
    * CUs badly spreads that round's K-tiles evenly over the CUs (fp32 partials of the tiles cut in pieces,
    * summed in K order: deterministic).  One GEMM at a time per scratch (stream order). */
   void* tail_ws;
+  /* Optional k-step-tiled copy of B (ptk_pack_kstep_tiles_bf16; B packed, ldb == K, N % 16 == 0; NULL = off), for a
+   * B that stays the same from call to call (a frozen weight).  The persistent 4- / 8-wave kernels stream their B
+   * pieces from it at batch 1; every other kernel family and launch shape reads B.  The result is bit-identical. */
+  const void* B_kt;
 } ptk_gemm_desc;
 int ptk_gemm(const ptk_gemm_desc* d, void* stream);
+/* The k-step-tiled copy of a packed row-major bf16 matrix B[N][K] (N % 16 == 0, K % 32 == 0), of the same byte
+ * size: the 1-KiB block (g, s) at byte (g * (K / 32) + s) * 1024 holds rows 16g .. 16g + 15 of k elements 32s ..
+ * 32s + 31; its 16-byte unit i (0..63) holds row 16g + (i >> 2), 16-byte k-chunk (i & 3) ^ ((i >> 3) & 2).
+ * ptk_kstep_tile_offset: the byte offset of element (row, k) in the copy (host only, no device call). */
+int64_t ptk_kstep_tile_offset(int64_t row, int64_t k, int64_t K);
+int ptk_pack_kstep_tiles_bf16(const void* src, void* dst, int N, int K, void* stream);
 #define PTK_GEMM_TAIL_COUNTER_BYTES 16384
 size_t ptk_gemm_tail_scratch_bytes(void);
 /* Workgroups the stream-K plan spreads this GEMM's last tile round over (0: no split), for tests. */
@@ -242,6 +252,9 @@ typedef struct {
   const void* w2;    const float* b2;     /* bf16 [D, I], f32 [D] */
   const float* ln1_w; const float* ln1_b;
   const float* ln2_w; const float* ln2_b;
+  /* optional k-step-tiled copies of the four weights (ptk_pack_kstep_tiles_bf16, see ptk_gemm_desc.B_kt); NULL:
+   * the GEMM reads the row-major weight */
+  const void* wqkv_kt; const void* wo_kt; const void* w1_kt; const void* w2_kt;
 } ptk_siglip_layer;
 
 typedef struct {
@@ -303,6 +316,12 @@ typedef struct {
   const void* wd;    const void* wd_t;    /* bf16 [H, I], [I, H] */
   const float* ln_in; const float* ln_post_attn; const float* ln_pre_ff; const float* ln_post_ff;  /* [H] */
   const float* q_norm; const float* k_norm;                                                        /* [hd] */
+  /* optional k-step-tiled copies of the eight frozen weights above (ptk_pack_kstep_tiles_bf16, see
+   * ptk_gemm_desc.B_kt); NULL (always, for trainable weights): the GEMM reads the row-major weight */
+  const void* wqkv_kt; const void* wqkv_t_kt;
+  const void* wo_kt;   const void* wo_t_kt;
+  const void* wgu_kt;  const void* wgu_t_kt;
+  const void* wd_kt;   const void* wd_t_kt;
 } ptk_gemma3_layer;
 
 typedef struct {

@@ -34,7 +34,7 @@ class GemmDesc(C.Structure):
                 ("aux", c_void_p), ("aux2", c_void_p), ("ld_aux", c_int64),
                 ("aux_in", c_void_p), ("aux_in2", c_void_p), ("ld_aux_in", c_int64),
                 ("amap", RowMap), ("cmap", RowMap), ("resid16", c_void_p), ("ld_resid16", c_int64),
-                ("bf16_linear", c_int), ("tail_ws", c_void_p)]
+                ("bf16_linear", c_int), ("tail_ws", c_void_p), ("B_kt", c_void_p)]
 
 
 class FlashDesc(C.Structure):
@@ -66,7 +66,8 @@ class SiglipConfigC(C.Structure):
 class SiglipLayerC(C.Structure):
     _fields_ = [("wqkv", c_void_p), ("bqkv", c_void_p), ("wo", c_void_p), ("bo", c_void_p),
                 ("w1", c_void_p), ("b1", c_void_p), ("w2", c_void_p), ("b2", c_void_p),
-                ("ln1_w", c_void_p), ("ln1_b", c_void_p), ("ln2_w", c_void_p), ("ln2_b", c_void_p)]
+                ("ln1_w", c_void_p), ("ln1_b", c_void_p), ("ln2_w", c_void_p), ("ln2_b", c_void_p),
+                ("wqkv_kt", c_void_p), ("wo_kt", c_void_p), ("w1_kt", c_void_p), ("w2_kt", c_void_p)]
 
 
 class SiglipWeightsC(C.Structure):
@@ -91,7 +92,9 @@ class Gemma3LayerC(C.Structure):
     _fields_ = [("wqkv", c_void_p), ("wqkv_t", c_void_p), ("wo", c_void_p), ("wo_t", c_void_p),
                 ("wgu", c_void_p), ("wgu_t", c_void_p), ("wd", c_void_p), ("wd_t", c_void_p),
                 ("ln_in", c_void_p), ("ln_post_attn", c_void_p), ("ln_pre_ff", c_void_p),
-                ("ln_post_ff", c_void_p), ("q_norm", c_void_p), ("k_norm", c_void_p)]
+                ("ln_post_ff", c_void_p), ("q_norm", c_void_p), ("k_norm", c_void_p),
+                ("wqkv_kt", c_void_p), ("wqkv_t_kt", c_void_p), ("wo_kt", c_void_p), ("wo_t_kt", c_void_p),
+                ("wgu_kt", c_void_p), ("wgu_t_kt", c_void_p), ("wd_kt", c_void_p), ("wd_t_kt", c_void_p)]
 
 
 class Gemma3WeightsC(C.Structure):
@@ -160,6 +163,8 @@ SIGNATURES = {
                                      c_void_p, c_int64, c_int, c_int64, c_int64, c_int, c_int,
                                      c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
     "ptk_cast_f32_bf16": (c_int, [c_void_p, c_void_p, c_int64, c_void_p]),
+    "ptk_kstep_tile_offset": (c_int64, [c_int64, c_int64, c_int64]),
+    "ptk_pack_kstep_tiles_bf16": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "ptk_fill_normal_bf16": (c_int, [c_void_p, c_int64, c_uint64, c_float, c_float, c_void_p]),
     "ptk_gemm_timer_enable": (c_int, [c_int]),
     "ptk_gemm_force_small_tiles": (c_int, [c_int]),

@@ -35,6 +35,7 @@ GemmArgs to_args(const ptk_gemm_desc* d) {
   a.amap = to_map(d->amap); a.cmap = to_map(d->cmap);
   a.resid16 = (const bf16_t*)d->resid16; a.ld_resid16 = d->ld_resid16; a.bf16_linear = d->bf16_linear;
   a.tail_ws = d->tail_ws;
+  a.B_kt = (const bf16_t*)d->B_kt;
   return a;
 }
 
@@ -162,6 +163,10 @@ int ptk_transpose_rows_bf16(const void* in, int64_t ld_in, int map_g, int64_t ma
   return launch_transpose_rows((const bf16_t*)in, ld_in, m, rows, cols, (bf16_t*)out, ld_out, rows_pad, ST);
 }
 
+int64_t ptk_kstep_tile_offset(int64_t row, int64_t k, int64_t K) { return kstep_tile_offset(row, k, K); }
+int ptk_pack_kstep_tiles_bf16(const void* src, void* dst, int N, int K, void* stream) {
+  return launch_pack_kstep_tiles((const bf16_t*)src, (bf16_t*)dst, N, K, ST);
+}
 int ptk_cast_f32_bf16(const float* in, void* out, int64_t n, void* stream) {
   return launch_cast_f32_bf16(in, (bf16_t*)out, n, ST);
 }

@@ -792,8 +792,13 @@ int launch_gemm(const GemmArgs& a, int act, int out, int batch, hipStream_t st, 
   const dim3 grid_big((unsigned)((long)((a.M + BIG - 1) / BIG) * ((a.N + BIG - 1) / BIG)), 1, 1);
   switch (plan.path) {
     case GEMM_PATH_P8:
-    case GEMM_PATH_P8SK: return launch_gemm_p8(a, act, out, st, plan.tail, plan.tm);
-    case GEMM_PATH_W4: return launch_gemm_w4(a, act, out, st, 0);
+    case GEMM_PATH_P8SK:
+    case GEMM_PATH_W4: {
+      GemmArgs b = a;   // B's k-step-tiled copy goes along only where this launch may read it
+      if (!b_ktiled_ok(a, plan, act, batch)) b.B_kt = nullptr;
+      if (plan.path == GEMM_PATH_W4) return launch_gemm_w4(b, act, out, st, 0);
+      return launch_gemm_p8(b, act, out, st, plan.tail, plan.tm);
+    }
     case GEMM_PATH_BIG2:
       gemm_act_out(act, out, [&](auto A, auto O) {
         hipLaunchKernelGGL((gemm_big2_kernel<A(), O()>), grid_big, dim3(512), 0, st, a);

@@ -275,6 +275,29 @@ GemmPlan gemm_plan(const GemmArgs& a, int act, int out, int batch, const GemmPla
   return p;
 }
 
+// ============================================================================ the k-step-tiled copy of B
+// The persistent kernels stage B in 1-KiB pieces: 16 rows x one 32-deep k-step, lane i fetching row i >> 2, logical
+// 16-B chunk (i & 3) ^ ((i >> 3) & 2) (gemm_w4.hip).  From row-major B that is 16 half lines per piece; the tiled
+// copy stores each piece as the contiguous KiB its lanes write to LDS, 8 whole 128-B lines, the k-steps of a 16-row
+// group g one after the other: block (g, s) at byte (g K/32 + s) 1024, unit i of it as above.  So element (row, k)
+// sits in unit 4 (row & 15) + (chunk ^ ((row >> 1) & 2)) of block (row / 16, k / 32), chunk = (k / 8) & 3.  Groups
+// are ordered row-major: every row >= N lies at or past byte N K 2, outside the buffer range, and reads as zero.
+long kstep_tile_offset(long row, long k, long K) {
+  const long rr = row & 15, chunk = (k >> 3) & 3;
+  const long unit = 4 * rr + (chunk ^ ((rr >> 1) & 2));
+  return ((row >> 4) * (K / 32) + (k >> 5)) * 1024 + unit * 16 + (k & 7) * 2;
+}
+
+// a launch reads B_kt only on the families whose B pieces are 16 rows x 64 B, at batch 1, from a packed B (ldb ==
+// K), under an epilogue that has a tiled kernel variant (bkt_act).  K slices never take it either (a slice's k-steps
+// are not a prefix of a group's stream), but no plan that reaches launch_gemm carries slices: their callers drop the
+// pointer themselves (gemm_split in models.cpp, launch_gemm_p8_kslices in gemm_w4.hip)
+bool b_ktiled_ok(const GemmArgs& a, const GemmPlan& plan, int act, int batch) {
+  if (!a.B_kt || batch != 1 || !bkt_act(act)) return false;
+  if (plan.path != GEMM_PATH_W4 && plan.path != GEMM_PATH_P8 && plan.path != GEMM_PATH_P8SK) return false;
+  return a.ldb == a.K && a.K % 32 == 0 && a.N % 16 == 0 && !((uintptr_t)a.B_kt & 15);
+}
+
 // ============================================================================ gemm_split's rule
 // Split-K for long-K GEMMs whose 256x256 tile grid fills few of the CUs' rounds (measured, tools/splitk_probe.py
 // r02: the cfg4 shapes dW_qkv 313 -> 73 us and dW_o 313 -> 68 us at 4 slices; dW_down, dW_gate|up, the

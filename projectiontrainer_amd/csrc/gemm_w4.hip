@@ -48,7 +48,9 @@
 
 namespace ptk {
 
-template <int ACT, int OUT, bool LEAN = false>
+// BKT: B is streamed from its k-step-tiled copy p.B_kt (a compile-time form: the stride of the B stream as one more
+// live scalar costs the 8-wave kernels SGPR spills, tests/test_asm_hazards.py)
+template <int ACT, int OUT, bool LEAN = false, bool BKT = false>
 __global__ void __launch_bounds__(256, 1) gemm_w4_kernel(GemmArgs p, uint32_t a_bytes, uint32_t b_bytes,
                                                          uint32_t c_bytes) {
   __shared__ __attribute__((aligned(16))) char smem[W4_NSLOT * W4_SLOT];   // 160 KiB: the k-step ring
@@ -69,7 +71,11 @@ __global__ void __launch_bounds__(256, 1) gemm_w4_kernel(GemmArgs p, uint32_t a_
   const int total_ks = ((ntile - loc + G - 1) / G) * nks;
 
   // A rows past M / B rows past N fall outside num_records and read as zero
-  const u32x4_t rsa = w4_rsrc(p.A, a_bytes), rsb = w4_rsrc(p.B, b_bytes);
+  // BKT: B from its k-step-tiled copy (gemm_plan.cpp kstep_tile_offset; the launch: b_ktiled_ok): the same
+  // bytes reach the same LDS units, each piece as one contiguous KiB (8 whole lines) instead of 16 half lines
+  constexpr bool bkt = BKT;
+  constexpr uint32_t bks = BKT ? 1024u : (uint32_t)(W4_KS * 2);   // bytes a k-step advances the B stream
+  const u32x4_t rsa = w4_rsrc(p.A, a_bytes), rsb = w4_rsrc(bkt ? p.B_kt : p.B, b_bytes);
 
   // ---- global -> LDS stream, one ring slot (32 KiB: A and B, 256 rows x 64 B each) per k-step.
   // Wave w fills rows 64w..64w+63 of both operands: 4 + 4 pieces of 16 rows x 64 B.  Lane i of a
@@ -82,7 +88,8 @@ __global__ void __launch_bounds__(256, 1) gemm_w4_kernel(GemmArgs p, uint32_t a_
     const int lr = wave * 64 + 16 * j + (lane >> 2);
     const int lc = (lane & 3) ^ ((lane >> 3) & 2);
     offa[j] = (uint32_t)lr * (uint32_t)p.lda * 2u + lc * 16;
-    offb[j] = (uint32_t)lr * (uint32_t)p.ldb * 2u + lc * 16;
+    offb[j] = bkt ? (uint32_t)(wave * 4 + j) * (uint32_t)p.K * 32u + lane * 16   // 16-row group 4w + j: K/32 blocks of 1 KiB
+                  : (uint32_t)lr * (uint32_t)p.ldb * 2u + lc * 16;
   }
   const uint32_t lds_base = __builtin_amdgcn_readfirstlane(lds_addr(smem));
   const uint32_t lds_dma = lds_base + wave * 64 * 64;      // this wave's rows in a slot
@@ -152,7 +159,7 @@ __global__ void __launch_bounds__(256, 1) gemm_w4_kernel(GemmArgs p, uint32_t a_
     constexpr bool first = decltype(first_c)::value;
     const uint32_t ba = frag_a + rs, bb = frag_b + rs;
     const uint32_t da = lds_dma + ws, db = da + W4_SOPB;
-    const uint32_t sa = dsa + dks * (W4_KS * 2), sb = dsb + dks * (W4_KS * 2);
+    const uint32_t sa = dsa + dks * (W4_KS * 2), sb = dsb + dks * bks;
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
 #if PTK_W4_RDS == 1
@@ -194,7 +201,7 @@ __global__ void __launch_bounds__(256, 1) gemm_w4_kernel(GemmArgs p, uint32_t a_
 #pragma unroll
   for (int b = 0; b < 4; ++b) {
     const uint32_t da = lds_dma + b * W4_SLOT, db = da + W4_SOPB;
-    const uint32_t sa = dsa + dks * (W4_KS * 2), sb = dsb + dks * (W4_KS * 2);
+    const uint32_t sa = dsa + dks * (W4_KS * 2), sb = dsb + dks * bks;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       W4_DMA(rsa, offa[j], sa, da + j * 1024);
@@ -275,6 +282,19 @@ __global__ void __launch_bounds__(256, 1) gemm_w4_kernel(GemmArgs p, uint32_t a_
 // PTK_LEAN_EPI=0 (A/B builds, PTK_AB) keeps the general epilogue (bit-identical either way)
 bool lean_epilogue_enabled() { return PTK_AB("PTK_LEAN_EPI", 1) != 0; }
 
+// The kernel variant of a launch: BKT where the launch streams B's k-step-tiled copy (launch_gemm leaves B_kt set only
+// where b_ktiled_ok holds, which includes bkt_act: the GELU-erf epilogues have no tiled variant).
+template <int ACT, int OUT, bool LEAN>
+static void w4_launch(const GemmArgs& a, long grid, hipStream_t st, uint32_t ab, uint32_t bb, uint32_t cb) {
+  if constexpr (bkt_act(ACT)) {
+    if (a.B_kt) {
+      hipLaunchKernelGGL((gemm_w4_kernel<ACT, OUT, LEAN, true>), dim3((unsigned)grid), dim3(256), 0, st, a, ab, bb, cb);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((gemm_w4_kernel<ACT, OUT, LEAN, false>), dim3((unsigned)grid), dim3(256), 0, st, a, ab, bb, cb);
+}
+
 int launch_gemm_w4(const GemmArgs& a, int act, int out, hipStream_t st, int max_grid) {
   const long ntile = (long)((a.M + W4 - 1) / W4) * ((a.N + W4 - 1) / W4);
   long grid = std::min<long>(ntile, max_grid > 0 ? max_grid : device_cus());
@@ -286,9 +306,9 @@ int launch_gemm_w4(const GemmArgs& a, int act, int out, hipStream_t st, int max_
   const uint32_t bb = (uint32_t)std::min<double>((double)a.N * a.ldb * 2, 2147483000.0);
   uint32_t cb = 0;
   if (lean_epilogue_ok(a, act, out, cb, lean_epilogue_enabled())) {
-#define PTK_W4L_CASE(ACT_)                                                                                   \
-    if (act == ACT_)                                                                                         \
-      hipLaunchKernelGGL((gemm_w4_kernel<ACT_, OUT_BF16, true>), dim3((unsigned)grid), dim3(256), 0, st, a, ab, bb, cb);
+#define PTK_W4L_CASE(ACT_) \
+    if (act == ACT_)       \
+      w4_launch<ACT_, OUT_BF16, true>(a, grid, st, ab, bb, cb);
     PTK_W4L_CASE(ACT_NONE)
     PTK_W4L_CASE(ACT_GELU_TANH)
     PTK_W4L_CASE(ACT_GEGLU_BWD)
@@ -296,7 +316,7 @@ int launch_gemm_w4(const GemmArgs& a, int act, int out, hipStream_t st, int max_
     return hipGetLastError() == hipSuccess ? 0 : set_error("gemm_w4 launch failed");
   }
   if (!gemm_act_out(act, out, [&](auto A, auto O) {
-        hipLaunchKernelGGL((gemm_w4_kernel<A(), O()>), dim3((unsigned)grid), dim3(256), 0, st, a, ab, bb, 0u);
+        w4_launch<A(), O(), false>(a, grid, st, ab, bb, 0u);
       }))
     return set_error("gemm_w4: unsupported (act=%d, out=%d)", act, out);
   return hipGetLastError() == hipSuccess ? 0 : set_error("gemm_w4 launch failed");
@@ -353,7 +373,7 @@ constexpr int P8_PIECES = 4;   // LDS-DMA pieces per wave per k-step
 // better where 256-row tiles leave a thin last round: Gemma3's N 1152 / 1024 projections at M 22 528 (440 -> 505
 // tiles of 7/8 the work on 2 rounds), N 1536 (3 rounds either way, 7/8 the work), SigLIP's q|k|v at M 18 432,
 // its fc1 on 192-row tiles (5 rounds of 256 -> 6 of 192) -- launch_gemm: p8_tile_height
-template <int ACT, int OUT, bool SK, bool LEAN = false, int TM = 256>
+template <int ACT, int OUT, bool SK, bool LEAN = false, int TM = 256, bool BKT = false>
 __global__ void __launch_bounds__(512, 1) gemm_p8_kernel(GemmArgs p, uint32_t a_bytes, uint32_t b_bytes, P8Tail tl,
                                                          uint32_t c_bytes) {
   static_assert(TM == 256 || ((TM == 224 || TM == 192 || TM == 160) && !SK), "shorter tiles: whole tiles only");
@@ -420,7 +440,11 @@ __global__ void __launch_bounds__(512, 1) gemm_p8_kernel(GemmArgs p, uint32_t a_
       k0 = (int)(b & 0xffffu); k1 = (int)(b >> 16);
     }
   };
-  const u32x4_t rsa = w4_rsrc(p.A, a_bytes), rsb = w4_rsrc(p.B, b_bytes);
+  // BKT: B from its k-step-tiled copy (gemm_plan.cpp kstep_tile_offset; the launch: b_ktiled_ok): the same
+  // bytes reach the same LDS units, each piece as one contiguous KiB (8 whole lines) instead of 16 half lines
+  constexpr bool bkt = BKT;
+  constexpr uint32_t bks = BKT ? 1024u : (uint32_t)(W4_KS * 2);   // bytes a k-step advances the B stream
+  const u32x4_t rsa = w4_rsrc(p.A, a_bytes), rsb = w4_rsrc(bkt ? p.B_kt : p.B, b_bytes);
 
   // global -> LDS: wave w fills rows 32w..32w+31 of both operands (2 + 2 pieces of 16 rows x 64 B), lane i of
   // a piece writes LDS row 16j + (i>>2), chunk i&3 and fetches logical chunk (i&3) ^ ((row>>1)&2) (w4's swizzle)
@@ -430,7 +454,8 @@ __global__ void __launch_bounds__(512, 1) gemm_p8_kernel(GemmArgs p, uint32_t a_
     const int lr = wave * 32 + 16 * j + (lane >> 2);
     const int lc = (lane & 3) ^ ((lane >> 3) & 2);
     offa[j] = (uint32_t)lr * (uint32_t)p.lda * 2u + lc * 16;
-    offb[j] = (uint32_t)lr * (uint32_t)p.ldb * 2u + lc * 16;
+    offb[j] = bkt ? (uint32_t)(wave * 2 + j) * (uint32_t)p.K * 32u + lane * 16   // 16-row group 2w + j
+                  : (uint32_t)lr * (uint32_t)p.ldb * 2u + lc * 16;
   }
   const uint32_t lds_base = __builtin_amdgcn_readfirstlane(lds_addr(smem));
   const uint32_t lds_dma = lds_base + wave * 32 * 64;
@@ -451,7 +476,7 @@ __global__ void __launch_bounds__(512, 1) gemm_p8_kernel(GemmArgs p, uint32_t a_
     }
     dsa = __builtin_amdgcn_readfirstlane((uint32_t)(bm * TM + (int)p.amap.off) * (uint32_t)p.lda * 2u + kz +
                                          (uint32_t)k0 * (W4_KT * 2));
-    dsb = __builtin_amdgcn_readfirstlane((uint32_t)(bn * W4) * (uint32_t)p.ldb * 2u + kz + (uint32_t)k0 * (W4_KT * 2));
+    dsb = __builtin_amdgcn_readfirstlane((uint32_t)(bn * W4) * (uint32_t)p.ldb * 2u + kz + (uint32_t)k0 * (2u * bks));
     dlen = 2 * (k1 - k0);
   };
   auto dma_advance = [&]() {
@@ -495,7 +520,7 @@ __global__ void __launch_bounds__(512, 1) gemm_p8_kernel(GemmArgs p, uint32_t a_
     constexpr int half = decltype(half_c)::value;
     const uint32_t ba = frag_a + rs, bb = frag_b + rs;
     const uint32_t da = lds_dma + ws, db = da + W4_SOPB;
-    const uint32_t sa = dsa + dks * (W4_KS * 2), sb = dsb + dks * (W4_KS * 2);
+    const uint32_t sa = dsa + dks * (W4_KS * 2), sb = dsb + dks * bks;
 #pragma unroll
     for (int q = 0; q < RB; ++q) {
       // n_q = RB - 2, RB, RB, RB + 1, RB + 2, .. (8 groups: 6, 8, 8, 9, 10, 10, 10, 10; each A read fewer, one less)
@@ -573,7 +598,7 @@ __global__ void __launch_bounds__(512, 1) gemm_p8_kernel(GemmArgs p, uint32_t a_
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
       const uint32_t da = lds_dma + b * W4_SLOT, db = da + W4_SOPB;
-      const uint32_t sa = dsa + dks * (W4_KS * 2), sb = dsb + dks * (W4_KS * 2);
+      const uint32_t sa = dsa + dks * (W4_KS * 2), sb = dsb + dks * bks;
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         if (a_dma) W4_DMA(rsa, offa[j], sa, da + j * 1024);
@@ -762,6 +787,7 @@ int launch_gemm_p8_kslices(const GemmArgs& a, int slices, hipStream_t st) {
     return set_error("gemm_p8_kslices: operands past 4 GiB");
   GemmArgs g = a;
   g.M = a.M * slices;
+  g.B_kt = nullptr;   // a slice's k-steps are not a prefix of a 16-row group's tiled stream: row-major B
   P8Tail tl;
   tl.zslices = slices;
   const long ntile = (long)(g.M / W4) * ((g.N + W4 - 1) / W4);
@@ -773,6 +799,20 @@ int launch_gemm_p8_kslices(const GemmArgs& a, int slices, hipStream_t st) {
   return hipGetLastError() == hipSuccess ? 0 : set_error("gemm_p8_kslices launch failed");
 }
 
+template <int ACT, int OUT, bool SK, bool LEAN, int TM>
+static void p8_launch(const GemmArgs& a, long grid, hipStream_t st, uint32_t ab, uint32_t bb, const P8Tail& tl,
+                      uint32_t cb) {
+  if constexpr (bkt_act(ACT)) {
+    if (a.B_kt) {
+      hipLaunchKernelGGL((gemm_p8_kernel<ACT, OUT, SK, LEAN, TM, true>), dim3((unsigned)grid), dim3(512), 0, st, a, ab,
+                         bb, tl, cb);
+      return;
+    }
+  }
+  hipLaunchKernelGGL((gemm_p8_kernel<ACT, OUT, SK, LEAN, TM, false>), dim3((unsigned)grid), dim3(512), 0, st, a, ab, bb,
+                     tl, cb);
+}
+
 template <int TM>
 static int launch_p8_short(const GemmArgs& a, int act, int out, hipStream_t st, long grid, bool lean_epi) {
   const uint32_t ab = (uint32_t)std::min<double>((double)(a.M + a.amap.off) * a.lda * 2, 2147483000.0);
@@ -781,23 +821,17 @@ static int launch_p8_short(const GemmArgs& a, int act, int out, hipStream_t st, 
   uint32_t cb = 0;
   if (lean_epilogue_ok(a, act, out, cb, lean_epi)) {
     if (act == ACT_NONE)
-      hipLaunchKernelGGL((gemm_p8_kernel<ACT_NONE, OUT_BF16, false, true, TM>), dim3((unsigned)grid), dim3(512), 0,
-                         st, a, ab, bb, tl, cb);
+      p8_launch<ACT_NONE, OUT_BF16, false, true, TM>(a, grid, st, ab, bb, tl, cb);
     else
-      hipLaunchKernelGGL((gemm_p8_kernel<ACT_GELU_TANH, OUT_BF16, false, true, TM>), dim3((unsigned)grid),
-                         dim3(512), 0, st, a, ab, bb, tl, cb);
+      p8_launch<ACT_GELU_TANH, OUT_BF16, false, true, TM>(a, grid, st, ab, bb, tl, cb);
   } else if (act == ACT_GELU_TANH) {
-    hipLaunchKernelGGL((gemm_p8_kernel<ACT_GELU_TANH, OUT_BF16, false, false, TM>), dim3((unsigned)grid), dim3(512),
-                       0, st, a, ab, bb, tl, 0u);
+    p8_launch<ACT_GELU_TANH, OUT_BF16, false, false, TM>(a, grid, st, ab, bb, tl, 0u);
   } else if (out == OUT_BF16) {
-    hipLaunchKernelGGL((gemm_p8_kernel<ACT_NONE, OUT_BF16, false, false, TM>), dim3((unsigned)grid), dim3(512), 0,
-                       st, a, ab, bb, tl, 0u);
+    p8_launch<ACT_NONE, OUT_BF16, false, false, TM>(a, grid, st, ab, bb, tl, 0u);
   } else if (out == OUT_F32) {
-    hipLaunchKernelGGL((gemm_p8_kernel<ACT_NONE, OUT_F32, false, false, TM>), dim3((unsigned)grid), dim3(512), 0,
-                       st, a, ab, bb, tl, 0u);
+    p8_launch<ACT_NONE, OUT_F32, false, false, TM>(a, grid, st, ab, bb, tl, 0u);
   } else {
-    hipLaunchKernelGGL((gemm_p8_kernel<ACT_NONE, OUT_F32_BFR, false, false, TM>), dim3((unsigned)grid), dim3(512),
-                       0, st, a, ab, bb, tl, 0u);
+    p8_launch<ACT_NONE, OUT_F32_BFR, false, false, TM>(a, grid, st, ab, bb, tl, 0u);
   }
   return hipGetLastError() == hipSuccess ? 0 : set_error("gemm_p8 launch failed");
 }
@@ -829,12 +863,10 @@ int launch_gemm_p8(const GemmArgs& a, int act, int out, hipStream_t st, const P8
   if (tl.units) {
     if (act != ACT_NONE) return set_error("gemm_p8: the stream-K tail takes ACT_NONE only (act=%d)", act);
     if (lean_epilogue_ok(a, act, out, cb, lean_epi)) {   // whole tiles take the lean epilogue
-      hipLaunchKernelGGL((gemm_p8_kernel<ACT_NONE, OUT_BF16, true, true>), dim3((unsigned)grid), dim3(512), 0, st, a,
-                         ab, bb, tl, cb);
+      p8_launch<ACT_NONE, OUT_BF16, true, true, 256>(a, grid, st, ab, bb, tl, cb);
     } else if (!gemm_act_out(act, out, [&](auto A, auto O) {
                  if constexpr (A() == ACT_NONE)   // (the tail kernel is instantiated for the plain epilogues only)
-                   hipLaunchKernelGGL((gemm_p8_kernel<ACT_NONE, O(), true>), dim3((unsigned)grid), dim3(512), 0, st, a,
-                                      ab, bb, tl, 0u);
+                   p8_launch<ACT_NONE, O(), true, false, 256>(a, grid, st, ab, bb, tl, 0u);
                })) {
       return set_error("gemm_p8: unsupported (act=%d, out=%d)", act, out);
     }
@@ -844,8 +876,7 @@ int launch_gemm_p8(const GemmArgs& a, int act, int out, hipStream_t st, const P8
   if (lean_epilogue_ok(a, act, out, cb, lean_epi)) {
 #define PTK_P8L_CASE(ACT_)                                                                                   \
     if (act == ACT_)                                                                                         \
-      hipLaunchKernelGGL((gemm_p8_kernel<ACT_, OUT_BF16, false, true>), dim3((unsigned)grid), dim3(512), 0, st, a, ab, \
-                         bb, tl, cb);
+      p8_launch<ACT_, OUT_BF16, false, true, 256>(a, grid, st, ab, bb, tl, cb);
     PTK_P8L_CASE(ACT_NONE)
     PTK_P8L_CASE(ACT_GELU_TANH)
     PTK_P8L_CASE(ACT_GEGLU_BWD)
@@ -853,7 +884,7 @@ int launch_gemm_p8(const GemmArgs& a, int act, int out, hipStream_t st, const P8
     return hipGetLastError() == hipSuccess ? 0 : set_error("gemm_p8 launch failed");
   }
   if (!gemm_act_out(act, out, [&](auto A, auto O) {
-        hipLaunchKernelGGL((gemm_p8_kernel<A(), O(), false>), dim3((unsigned)grid), dim3(512), 0, st, a, ab, bb, tl, 0u);
+        p8_launch<A(), O(), false, false, 256>(a, grid, st, ab, bb, tl, 0u);
       }))
     return set_error("gemm_p8: unsupported (act=%d, out=%d)", act, out);
   return hipGetLastError() == hipSuccess ? 0 : set_error("gemm_p8 launch failed");

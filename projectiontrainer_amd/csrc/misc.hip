@@ -97,6 +97,29 @@ int launch_im2col(const bf16_t* px, bf16_t* out, int B, int C, int H, int W, int
   RET_OK("im2col");
 }
 
+// k-step-tiled copy of a frozen weight (gemm_plan.cpp kstep_tile_offset): thread u writes 16-B unit u of dst, i.e.
+// unit i = u & 63 of block u >> 6 = g K/32 + s: source row 16 g + (i >> 2), logical 16-B chunk (i & 3) ^ ((i >> 3) & 2)
+// of k-step s.  Run once per weight at load.
+__global__ void __launch_bounds__(256) pack_kstep_tiles_kernel(const bf16_t* __restrict__ src, bf16_t* __restrict__ dst,
+                                                               long units, int ksteps) {
+  const long u = (long)blockIdx.x * 256 + threadIdx.x;
+  if (u >= units) return;
+  const int i = (int)(u & 63);
+  const long blk = u >> 6, g = blk / ksteps, s = blk - g * ksteps;
+  const long row = 16 * g + (i >> 2);
+  const int chunk = (i & 3) ^ ((i >> 3) & 2);
+  const uint4 v = *reinterpret_cast<const uint4*>(src + (row * ksteps + s) * 32 + chunk * 8);
+  *reinterpret_cast<uint4*>(dst + u * 8) = v;
+}
+int launch_pack_kstep_tiles(const bf16_t* src, bf16_t* dst, int N, int K, hipStream_t st) {
+  if (N <= 0 || K <= 0 || N % 16 || K % 32) return set_error("pack_kstep_tiles: N %d %% 16, K %d %% 32", N, K);
+  if (!src || !dst || (((uintptr_t)src | (uintptr_t)dst) & 15)) return set_error("pack_kstep_tiles: 16-B aligned src / dst");
+  const long units = (long)N * K / 8;
+  hipLaunchKernelGGL(pack_kstep_tiles_kernel, dim3((unsigned)((units + 255) / 256)), dim3(256), 0, st, src, dst, units,
+                     K / 32);
+  RET_OK("pack_kstep_tiles");
+}
+
 __global__ void cast_f32_bf16_kernel(const float* __restrict__ in, bf16_t* __restrict__ out, long n) {
   const long i = ((long)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i + 3 < n) {

@@ -114,8 +114,12 @@ static bool ce_two_pass() {
   return v != 0;
 }
 
-GemmArgs gemm(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K) {
+// B_kt: the k-step-tiled copy of a frozen weight B, if its layer struct carries one (launch_gemm decides whether the
+// launch reads it)
+GemmArgs gemm(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
+              const void* B_kt = nullptr) {
   GemmArgs g;
+  g.B_kt = (const bf16_t*)B_kt;
   g.A = (const bf16_t*)A; g.B = (const bf16_t*)B; g.C = C;
   g.lda = lda; g.ldb = ldb; g.ldc = ldc;
   g.M = M; g.N = N; g.K = K;
@@ -289,6 +293,7 @@ int gemm_split(const GemmArgs& a, int out, float* part, long part_floats, hipStr
   }
   const int kc = sp.kc, nfull = sp.slices, rem = sp.rem;
   GemmArgs b = a;
+  b.B_kt = nullptr;   // K slices read row-major B
   b.C = part; b.ldc = a.N; b.K = kc;
   b.sA0 = kc; b.sB0 = kc; b.sC0 = (long)a.M * a.N;
   b.bf16_linear = 0; b.resid16 = nullptr; b.ld_resid16 = 0;
@@ -416,7 +421,7 @@ int ptk_siglip_fwd(const ptk_siglip_config* c, const ptk_siglip_weights* wt, int
     sq.next("siglip.attn");
     CK(launch_layernorm_bf16(w.h, L.ln1_w, L.ln1_b, w.a, M, D, c->eps, st));
     {  // fused q|k|v projection
-      GemmArgs g = gemm(w.a, D, L.wqkv, D, w.qkv, 3 * D, M, 3 * D, D);
+      GemmArgs g = gemm(w.a, D, L.wqkv, D, w.qkv, 3 * D, M, 3 * D, D, L.wqkv_kt);
       g.bias = L.bqkv;
       CK(launch_gemm(g, ACT_NONE, OUT_BF16, 1, st));
     }
@@ -433,19 +438,19 @@ int ptk_siglip_fwd(const ptk_siglip_config* c, const ptk_siglip_weights* wt, int
       CK(launch_attn_fwd(fa, B * Hh, st));
     }
     {  // h = bf16(h + bf16(out_proj + bias))   (modeling_siglip.py:343-346, bf16 module)
-      GemmArgs g = gemm(w.o, D, L.wo, D, w.h, D, M, D, D);
+      GemmArgs g = gemm(w.o, D, L.wo, D, w.h, D, M, D, D, L.wo_kt);
       g.bias = L.bo; g.bf16_linear = 1; g.resid16 = w.h; g.ld_resid16 = D;
       CK(launch_gemm(g, ACT_NONE, OUT_BF16, 1, st));
     }
     sq.next("siglip.mlp");
     CK(launch_layernorm_bf16(w.h, L.ln2_w, L.ln2_b, w.a, M, D, c->eps, st));
     {
-      GemmArgs g = gemm(w.a, D, L.w1, D, w.mlp, I, M, I, D);
+      GemmArgs g = gemm(w.a, D, L.w1, D, w.mlp, I, M, I, D, L.w1_kt);
       g.bias = L.b1;
       CK(launch_gemm(g, ACT_GELU_TANH, OUT_BF16, 1, st));
     }
     {  // h = bf16(h + bf16(fc2 + bias))
-      GemmArgs g = gemm(w.mlp, I, L.w2, I, w.h, D, M, D, I);
+      GemmArgs g = gemm(w.mlp, I, L.w2, I, w.h, D, M, D, I, L.w2_kt);
       g.bias = L.b2; g.bf16_linear = 1; g.resid16 = w.h; g.ld_resid16 = D;
       CK(launch_gemm(g, ACT_NONE, OUT_BF16, 1, st));
     }
@@ -524,7 +529,7 @@ int gemma_run(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, const pt
     bf16_t* xff = train ? sv.xn_ff : w.xn;
     bf16_t* hh = train ? sv.h : w.h;
     sq.next("gemma.fwd.attn");
-    CK(gemm_split(gemm(xin, H, L.wqkv, H, sv.qkv, Dqkv, M, Dqkv, H), OUT_BF16, w.skpart, w.sk_floats, st));
+    CK(gemm_split(gemm(xin, H, L.wqkv, H, sv.qkv, Dqkv, M, Dqkv, H, L.wqkv_kt), OUT_BF16, w.skpart, w.sk_floats, st));
     CK(launch_qknorm_rope_fwd(sv.qkv, L.q_norm, L.k_norm, cs, sn, ash, eps, sv.Q, sv.K, sv.V, sv.rstd_q, sv.rstd_k,
                               st));
     {  // causal / sliding-window GQA attention, flash; O token-major, LSE kept for the backward
@@ -543,24 +548,24 @@ int gemma_run(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, const pt
       StageScope sf("gemma.fwd.flash", st);
       CK(launch_attn_fwd(fa, Z, st));
     }
-    CK(gemm_split(gemm(sv.O, Dq, L.wo, Dq, sv.ao, H, M, H, Dq), OUT_BF16, w.skpart, w.sk_floats, st));
+    CK(gemm_split(gemm(sv.O, Dq, L.wo, Dq, sv.ao, H, M, H, Dq, L.wo_kt), OUT_BF16, w.skpart, w.sk_floats, st));
     CK(launch_residual_norm_fwd(sv.ao, w.x[l], L.ln_post_attn, L.ln_pre_ff, sv.x2, xff, sv.rstd_ao, sv.rstd_pre, M,
                                 H, eps, st));
     sq.next("gemma.fwd.mlp");
     if (l + 1 < nl) {
-      GemmArgs g = gemm(xff, H, L.wgu, H, hh, I, M, 2 * I, H);
+      GemmArgs g = gemm(xff, H, L.wgu, H, hh, I, M, 2 * I, H, L.wgu_kt);
       g.aux = sv.glu_a; g.aux2 = sv.glu_b; g.ld_aux = I;
       CK(launch_gemm(g, ACT_GEGLU, OUT_BF16, 1, st));
-      CK(gemm_split(gemm(hh, I, L.wd, I, sv.dn, H, M, H, I), OUT_BF16, w.skpart, w.sk_floats, st));
+      CK(gemm_split(gemm(hh, I, L.wd, I, sv.dn, H, M, H, I, L.wd_kt), OUT_BF16, w.skpart, w.sk_floats, st));
     } else {
       // last layer: only the loss rows reach the loss, so its MLP runs on those R rows (h, glu_a, glu_b compact);
       // the other rows of dn are zero (their residual output is never read, their gradient is zero)
-      GemmArgs g = gemm(xff, H, L.wgu, H, hh, I, R, 2 * I, H);
+      GemmArgs g = gemm(xff, H, L.wgu, H, hh, I, R, 2 * I, H, L.wgu_kt);
       g.amap = lossmap;
       g.aux = sv.glu_a; g.aux2 = sv.glu_b; g.ld_aux = I;
       CK(launch_gemm(g, ACT_GEGLU, OUT_BF16, 1, st));
       CK(launch_zero(sv.dn, (size_t)M * H * sizeof(bf16_t), st));
-      GemmArgs g2 = gemm(hh, I, L.wd, I, sv.dn, H, R, H, I);
+      GemmArgs g2 = gemm(hh, I, L.wd, I, sv.dn, H, R, H, I, L.wd_kt);
       g2.cmap = lossmap;
       CK(launch_gemm(g2, ACT_NONE, OUT_BF16, 1, st));
     }
@@ -651,25 +656,25 @@ int gemma_run(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, const pt
     // GEMM + one streaming geglu_bwd pass instead (A/B)
     if (!last) {
       if (geglu_split()) {
-        CK(launch_gemm(gemm(w.dao, H, L.wd_t, H, w.h, I, M, I, H), ACT_NONE, OUT_BF16, 1, st));
+        CK(launch_gemm(gemm(w.dao, H, L.wd_t, H, w.h, I, M, I, H, L.wd_t_kt), ACT_NONE, OUT_BF16, 1, st));
         CK(launch_geglu_bwd(w.h, sv.glu_a, sv.glu_b, w.dgu, M, I, st));
       } else {
-        GemmArgs g = gemm(w.dao, H, L.wd_t, H, w.dgu, 2 * I, M, I, H);
+        GemmArgs g = gemm(w.dao, H, L.wd_t, H, w.dgu, 2 * I, M, I, H, L.wd_t_kt);
         g.aux_in = sv.glu_a;
         g.aux_in2 = sv.glu_b;
         g.ld_aux_in = I;
         CK(launch_gemm(g, ACT_GEGLU_BWD, OUT_BF16, 1, st));
       }
       if (train) CK(weight_grad(w.dgu, 2 * I, ident, 2 * I, sv.xn_ff, H, ident, H, M, w.TA, w.TB, GL->wgu, w.skpart, w.sk_floats, st));
-      CK(gemm_split(gemm(w.dgu, 2 * I, L.wgu_t, 2 * I, w.dtmp, H, M, H, 2 * I), OUT_BF16, w.skpart, w.sk_floats, st));
+      CK(gemm_split(gemm(w.dgu, 2 * I, L.wgu_t, 2 * I, w.dtmp, H, M, H, 2 * I, L.wgu_t_kt), OUT_BF16, w.skpart, w.sk_floats, st));
     } else {   // last layer: MLP gradient is non-zero on the loss rows only (compact h, glu_a, glu_b, dgu)
-      GemmArgs g = gemm(w.dao, H, L.wd_t, H, w.h, I, R, I, H);
+      GemmArgs g = gemm(w.dao, H, L.wd_t, H, w.h, I, R, I, H, L.wd_t_kt);
       g.amap = lossmap;
       CK(launch_gemm(g, ACT_NONE, OUT_BF16, 1, st));
       CK(launch_geglu_bwd(w.h, sv.glu_a, sv.glu_b, w.dgu, R, I, st));
       if (train) CK(weight_grad(w.dgu, 2 * I, ident, 2 * I, sv.xn_ff, H, lossmap, H, R, w.TA, w.TB, GL->wgu, w.skpart, w.sk_floats, st));
       CK(launch_zero(w.dtmp, (size_t)M * H * sizeof(bf16_t), st));
-      GemmArgs g2 = gemm(w.dgu, 2 * I, L.wgu_t, 2 * I, w.dtmp, H, R, H, 2 * I);
+      GemmArgs g2 = gemm(w.dgu, 2 * I, L.wgu_t, 2 * I, w.dtmp, H, R, H, 2 * I, L.wgu_t_kt);
       g2.cmap = lossmap;
       CK(launch_gemm(g2, ACT_NONE, OUT_BF16, 1, st));
     }
@@ -680,7 +685,7 @@ int gemma_run(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, const pt
     if (train)
       CK(weight_grad(w.dao, H, ident, H, sv.O, Dq, ident, Dq, M, w.TA, w.TB, GL->wo, w.skpart, w.sk_floats, st));
     {  // dO (Q layout) = dao . Wo, one GEMM per kv head group of output columns
-      GemmArgs g = gemm(w.dao, H, L.wo_t, H, w.dO, (long)G * D, M, G * D, H);
+      GemmArgs g = gemm(w.dao, H, L.wo_t, H, w.dO, (long)G * D, M, G * D, H, L.wo_t_kt);
       g.sB0 = (long)G * D * H; g.sC0 = (long)Sp * G * D;
       g.cmap = RowMap{Sp, 0, (long)Hkv * Sp, 0};
       CK(launch_gemm(g, ACT_NONE, OUT_BF16, Hkv, st));
@@ -710,7 +715,7 @@ int gemma_run(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, const pt
                              (bf16_t*)GL->k_norm, w.wpart, st));
       CK(weight_grad(w.dqkv, Dqkv, ident, Dqkv, sv.xn_in, H, ident, H, M, w.TA, w.TB, GL->wqkv, w.skpart, w.sk_floats, st));
     }
-    CK(gemm_split(gemm(w.dqkv, Dqkv, L.wqkv_t, Dqkv, w.dtmp, H, M, H, Dqkv), OUT_BF16, w.skpart, w.sk_floats, st));
+    CK(gemm_split(gemm(w.dqkv, Dqkv, L.wqkv_t, Dqkv, w.dtmp, H, M, H, Dqkv, L.wqkv_t_kt), OUT_BF16, w.skpart, w.sk_floats, st));
     if (l > 0) {
       // dR += rms_bwd(x_l, ln_in, dtmp), then layer l-1's post-ff norm backward on the new dR -> dao
       const ptk_gemma3_layer& Lp = wt->layers[l - 1];

@@ -67,6 +67,10 @@ struct GemmArgs {
   // stream-K tail scratch of the persistent 8-wave kernel (gemm_w4.hip P8Tail, p8_tail_scratch_bytes); nullptr:
   // the calling thread's TailScratchScope, if any
   void* tail_ws = nullptr;
+  // optional k-step-tiled copy of B (gemm_plan.cpp kstep_tile_offset; frozen weights, packed once at load): the
+  // persistent 4- / 8-wave kernels stream their B pieces from it, one contiguous KiB each, when b_ktiled_ok holds;
+  // every other family reads B (bit-identical either way)
+  const bf16_t* B_kt = nullptr;
 };
 
 // kernel families launch_gemm dispatches to (census: path_counts, ptk_gemm_path_counts)
@@ -133,6 +137,14 @@ struct GemmPlan {
   bool single_round = false;   // the single-round predicate chose the 8-wave kernel (gemm_split_plan: no K split)
 };
 GemmPlan gemm_plan(const GemmArgs& a, int act, int out, int batch, const GemmPlanEnv& env);
+// the k-step-tiled copy of a row-major bf16 B[N][K] (K % 32 == 0, N % 16 == 0; same byte size): byte offset of
+// element (row, k), and whether the launch `plan` of these operands reads a.B_kt (the 4-wave / 8-wave / stream-K
+// families at batch 1, B packed with ldb == K, an epilogue with a tiled kernel variant: bkt_act)
+// the epilogues whose persistent kernels have a variant that streams the tiled copy: all but GELU-erf and its
+// backward, which only the trainable projector's GEMMs use (the one rule of b_ktiled_ok and the launchers)
+constexpr bool bkt_act(int act) { return act != ACT_GELU_ERF && act != ACT_GELU_ERF_BWD; }
+long kstep_tile_offset(long row, long k, long K);
+bool b_ktiled_ok(const GemmArgs& a, const GemmPlan& plan, int act, int batch);
 // validate, plan (or take `planned`, a plan gemm_plan made for these operands under the current env), launch
 int launch_gemm(const GemmArgs& a, int act, int out, int batch, hipStream_t st, const GemmPlan* planned = nullptr);
 // gemm_split's decision (models.cpp launches it).  kc == 0: launch_gemm directly (tail_ws: with the split-K scratch
@@ -381,6 +393,8 @@ size_t attn_bwd_workspace_bytes(const FlashBwdArgs& a, int nz);
 // output columns in [rows, rows_pad)
 int launch_transpose(const bf16_t* in, long ld_in, long sin0, long sin1, int zin, bf16_t* out, long ld_out,
                      long sout0, long sout1, int nz, int rows, int cols, int rows_pad, hipStream_t st);
+// dst = the k-step-tiled copy (gemm_plan.cpp kstep_tile_offset) of the packed row-major src [N][K], N % 16, K % 32
+int launch_pack_kstep_tiles(const bf16_t* src, bf16_t* dst, int N, int K, hipStream_t st);
 int launch_im2col(const bf16_t* px, bf16_t* out, int B, int C, int H, int W, int P, hipStream_t st);
 int launch_cast_f32_bf16(const float* in, bf16_t* out, long n, hipStream_t st);
 int launch_build_llm_inputs(const bf16_t* embed, const int64_t* ids, int B, int T, int Nv, int S, int Spad,

@@ -45,9 +45,16 @@ def rope_tables(cfg: Gemma3TextConfig, max_pos: int, sliding: bool):
     return f.cos().contiguous(), f.sin().contiguous()
 
 
+KT_KEYS = ("wqkv", "wqkv_t", "wo", "wo_t", "wgu", "wgu_t", "wd", "wd_t")   # Gemma3LayerC's *_kt fields, in order
+
+
 class Gemma3CausalLM:
-    def __init__(self, cfg: Gemma3TextConfig, params: dict | None, device="cuda", max_pos: int = 2048):
+    def __init__(self, cfg: Gemma3TextConfig, params: dict | None, device="cuda", max_pos: int = 2048,
+                 frozen: bool = True):
+        """frozen: the weights never change (Stage 1), so they get k-step-tiled copies for the persistent GEMMs;
+        a model built for Stage 2's unfrozen fine-tune passes False and never packs them."""
         self.cfg, self.device, self.max_pos = cfg, torch.device(device), max_pos
+        self.frozen = frozen
         self._ws = None
         if params is not None:
             self._load(params)
@@ -79,10 +86,21 @@ class Gemma3CausalLM:
         for lay in self.layers:
             for k in ("wqkv", "wo", "wgu", "wd"):
                 lay[k + "_t"] = K.transpose(lay[k])
+            # frozen weights: the k-step-tiled copies the persistent GEMMs stream their B operand from
+            for k in KT_KEYS:
+                lay[k + "_kt"] = K.frozen_kstep_tiles(lay[k]) if self.frozen else None
         self.embed_t = K.transpose(self.embed)
         tabs = [rope_tables(self.cfg, self.max_pos, s) for s in (True, False)]
         (self.cos_l, self.sin_l), (self.cos_g, self.sin_g) = [(c.to(self.device), s.to(self.device))
                                                               for c, s in tabs]
+
+    def drop_ktiled(self):
+        """Trainable weights (Stage 2) change every step: no k-step-tiled copies, the GEMMs read the weights.
+        (For a model that was built frozen; one built with frozen=False has none to drop.)"""
+        self.frozen = False
+        for lay in self.layers:
+            for k in KT_KEYS:
+                lay[k + "_kt"] = None
 
     @staticmethod
     def config_from_hf(c) -> Gemma3TextConfig:
@@ -128,11 +146,11 @@ class Gemma3CausalLM:
                              "(run without --enable_qlora)")
 
     @classmethod
-    def from_hf(cls, model, device="cuda", max_pos=2048):
+    def from_hf(cls, model, device="cuda", max_pos=2048, frozen=True):
         cls.check_not_quantized(model)
         cfg = cls.config_from_hf(model.config)
         sd = {k: v.detach().float() for k, v in model.state_dict().items()}
-        lm = cls(cfg, sd, device, max_pos)
+        lm = cls(cfg, sd, device, max_pos, frozen)
         # generate() without explicit sampling arguments uses the checkpoint's generation_config, as HF does (the
         # public gemma-3-1b-it ships top_k 64, top_p 0.95)
         gc = getattr(model, "generation_config", None)
@@ -142,9 +160,9 @@ class Gemma3CausalLM:
         return lm
 
     @classmethod
-    def random_init(cls, cfg: Gemma3TextConfig, device="cuda", seed=1, max_pos=2048):
+    def random_init(cls, cfg: Gemma3TextConfig, device="cuda", seed=1, max_pos=2048, frozen=True):
         """Synthetic bf16 weights generated on the device (N(0, 0.02^2); norm weights 0)."""
-        self = cls(cfg, None, device, max_pos)
+        self = cls(cfg, None, device, max_pos, frozen)
         dev = self.device
         H, I = cfg.hidden_size, cfg.intermediate_size
         s = [seed * 100000]
@@ -173,7 +191,7 @@ class Gemma3CausalLM:
                 "ln_post_ff", "q_norm", "k_norm")
         arr = (L.Gemma3LayerC * len(self.layers))()
         for i, lay in enumerate(self.layers):
-            arr[i] = L.Gemma3LayerC(*[lay[k].data_ptr() for k in keys])
+            arr[i] = L.Gemma3LayerC(*[lay[k].data_ptr() for k in keys], *[L.ptr(lay.get(k + "_kt")) for k in KT_KEYS])
         self._c_layers = arr
         self.c_w = L.Gemma3WeightsC(self.embed.data_ptr(), self.embed_t.data_ptr(), self.final_norm.data_ptr(),
                                     self.cos_l.data_ptr(), self.sin_l.data_ptr(), self.cos_g.data_ptr(),

@@ -3,6 +3,8 @@ tensors out, launched on torch's current HIP stream).  Used by the model
 classes and by the kernel parity tests."""
 from __future__ import annotations
 
+import os
+
 import torch
 
 from . import _lib as L
@@ -23,9 +25,11 @@ def _bits(t):
 def gemm(A, B, *, C=None, out_dtype=torch.bfloat16, act=L.ACT_NONE, alpha=1.0, bias=None, rowadd=None,
          resid=None, aux=None, aux2=None, aux_in=None, aux_in2=None, M=None, N=None, K=None,
          lda=None, ldb=None, ldc=None, batch=1, batch_inner=1, strides=(0, 0, 0, 0, 0, 0),
-         amap=(0, 0, 0, 0), cmap=(0, 0, 0, 0), out_mode=None, resid16=None, bf16_linear=False, tail_ws=None):
+         amap=(0, 0, 0, 0), cmap=(0, 0, 0, 0), out_mode=None, resid16=None, bf16_linear=False, tail_ws=None,
+         B_kt=None):
     """C = epi(alpha * A . B^T) with A [M,K], B [N,K] bf16 (K-contiguous).  tail_ws: stream-K tail scratch
-    (uint8 [ptk_gemm_tail_scratch_bytes], its counters zero)."""
+    (uint8 [ptk_gemm_tail_scratch_bytes], its counters zero).  B_kt: pack_kstep_tiles(B), for a B that stays the
+    same from call to call (the persistent kernels stream it; the result is bit-identical)."""
     _require_cuda(A, B)
     M = A.shape[-2] if M is None else M
     K = A.shape[-1] if K is None else K
@@ -61,6 +65,7 @@ def gemm(A, B, *, C=None, out_dtype=torch.bfloat16, act=L.ACT_NONE, alpha=1.0, b
         d.resid16, d.ld_resid16 = ptr(resid16), resid16.stride(-2)
     d.bf16_linear = int(bool(bf16_linear))
     d.tail_ws = ptr(tail_ws)
+    d.B_kt = ptr(B_kt)
     check(L.lib().ptk_gemm(d, L.stream_ptr(A.device)), "ptk_gemm")
     return C
 
@@ -185,6 +190,27 @@ def transpose(x, rows_pad=None, out=None):
     check(L.lib().ptk_transpose_bf16(ptr(x3), x3.stride(1), ptr(out), rp, Z, x3.stride(0), cols * rp, rows, cols, rp,
                                      L.stream_ptr(x.device)), "transpose")
     return out[0] if squeeze else out
+
+
+def pack_kstep_tiles(w):
+    """The k-step-tiled copy (include/ptk.h ptk_kstep_tile_offset) of a contiguous bf16 weight [N, K], N % 16 == 0,
+    K % 32 == 0: what gemm(..., B_kt=) and the *_kt fields of the frozen layers' weight structs take."""
+    _require_cuda(w)
+    if w.dim() != 2 or w.dtype != torch.bfloat16 or not w.is_contiguous():
+        raise L.PtkError("pack_kstep_tiles: a contiguous bf16 [N, K] matrix")
+    out = torch.empty_like(w)
+    check(L.lib().ptk_pack_kstep_tiles_bf16(ptr(w), ptr(out), w.shape[0], w.shape[1], L.stream_ptr(w.device)),
+          "pack_kstep_tiles")
+    return out
+
+
+def frozen_kstep_tiles(w):
+    """pack_kstep_tiles(w) for a frozen weight the persistent GEMMs stream as their B operand, or None: where the
+    shape has no tiled copy (N % 16, K % 32), or under PTK_B_KTILED=0 (the result-preserving A/B switch: every GEMM
+    reads the row-major weight, as before the copies existed)."""
+    if os.environ.get("PTK_B_KTILED", "1") == "0" or w.shape[0] % 16 or w.shape[1] % 32:
+        return None
+    return pack_kstep_tiles(w)
 
 
 def cast_bf16(x, out=None):

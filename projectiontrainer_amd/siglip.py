@@ -91,9 +91,12 @@ class SiglipVisionTower:
                                      c.num_attention_heads, c.intermediate_size, c.num_hidden_layers,
                                      c.layer_norm_eps)
         arr = (L.SiglipLayerC * len(self.layers))()
+        for lay in self.layers:   # the tower is frozen in both stages: k-step-tiled copies of its GEMM weights
+            lay["kt"] = {k: K.frozen_kstep_tiles(lay[k]) for k in ("wqkv", "wo", "w1", "w2")}
         for i, lay in enumerate(self.layers):
             arr[i] = L.SiglipLayerC(*[lay[k].data_ptr() for k in ("wqkv", "bqkv", "wo", "bo", "w1", "b1", "w2", "b2",
-                                                                   "ln1_w", "ln1_b", "ln2_w", "ln2_b")])
+                                                                   "ln1_w", "ln1_b", "ln2_w", "ln2_b")],
+                                    *[L.ptr(lay["kt"][k]) for k in ("wqkv", "wo", "w1", "w2")])
         self._c_layers = arr
         self.c_w = L.SiglipWeightsC(self.patch_w.data_ptr(), self.patch_b.data_ptr(), self.pos.data_ptr(),
                                     self.post_w.data_ptr(), self.post_b.data_ptr(),

@@ -96,6 +96,7 @@ class Gemma3TrainState:
                 lay[k] = self.view(f"{i}.{k}")
             for k in NORM_KEYS:
                 lay[k] = n32(f"{i}.{k}").view(self.offsets[f"{i}.{k}"][1])
+        llm.drop_ktiled()
         self.refresh()
         llm._build_c()
         self._build_grads_c()
@@ -309,7 +310,8 @@ class Stage2Engine:
 def synthetic_engine(cfg, device="cuda", seed=0, **kw):
     """Stage2Engine over random-init towers of the named architecture (benchmark; no checkpoints offline)."""
     vision = SiglipVisionTower.random_init(cfg.vision, device, seed)
-    llm = Gemma3CausalLM.random_init(cfg.text, device, seed + 1, max_pos=Gemma3CausalLM.seq_pad(cfg.seq_len))
+    llm = Gemma3CausalLM.random_init(cfg.text, device, seed + 1, max_pos=Gemma3CausalLM.seq_pad(cfg.seq_len),
+                                     frozen=False)   # trained here: no k-step-tiled copies
     torch.manual_seed(seed + 2)
     proj = MLPProjector(cfg.vision.hidden_size, cfg.text.hidden_size, cfg.expansion_factor, device=device)
     return Stage2Engine(vision, llm, proj, **kw)

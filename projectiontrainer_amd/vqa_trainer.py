@@ -102,7 +102,7 @@ class VQATrainerStage2:
         self.vision_encoder = vision_encoder if isinstance(vision_encoder, SiglipVisionTower) \
             else SiglipVisionTower.from_hf(vision_encoder, self.device)
         self.language_model = language_model if isinstance(language_model, Gemma3CausalLM) \
-            else Gemma3CausalLM.from_hf(language_model, self.device, max_pos=4096)
+            else Gemma3CausalLM.from_hf(language_model, self.device, max_pos=4096, frozen=False)
         if not isinstance(projection_layer, MLPProjector):
             sd = projection_layer.state_dict()
             p = MLPProjector(sd["model.0.weight"].shape[1], sd["model.2.weight"].shape[0])

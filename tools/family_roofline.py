@@ -35,20 +35,20 @@ def roles(cfg):
     # d(gate|up) dX, the standalone GEGLU backward)
     R = B * T
     return {
-        "gemm_p8_kernel<0, 0, false, true, 224>": [
+        "gemm_p8_kernel<0, 0, false, true, 224": [
             ("SigLIP q|k|v", Lv, 2 * M_v * D * 3 * D),
             ("Gemma o", L, 2 * M_g * q * H),
             ("Gemma d(q|k|v) dX", L, 2 * M_g * (q + 2 * kv) * H),
             ("Gemma down", L - 1, 2 * M_g * I * H),
             ("Gemma d(gate|up) dX", L - 1, 2 * M_g * 2 * I * H)],
-        "gemm_p8_kernel<0, 0, false, true, 192>": [
+        "gemm_p8_kernel<0, 0, false, true, 192": [
             ("Gemma q|k|v", L, 2 * M_g * H * (q + 2 * kv)),
             ("Gemma dO", L, 2 * M_g * H * q)],
-        "gemm_p8_kernel<0, 0, false, true, 160>": [("SigLIP o", Lv, 2 * M_v * D * D)],
+        "gemm_p8_kernel<0, 0, false, true, 160": [("SigLIP o", Lv, 2 * M_v * D * D)],
         "gemm_w4_kernel<3, 0,": [("Gemma gate|up + GEGLU", L - 1, 2 * M_g * 2 * I * H)],
         "gemm_w4_kernel<5, 0,": [("Gemma dh + GEGLU backward", L - 1, 2 * M_g * I * H)],
         "gemm_big_kernel<3, 0>": [("last layer gate|up + GEGLU (loss rows)", 1, 2 * R * 2 * I * H)],
-        "gemm_p8_kernel<0, 0, false, false, 160>": [("last layer down, dh, d(gate|up) dX (loss rows)", 3,
+        "gemm_p8_kernel<0, 0, false, false, 160": [("last layer down, dh, d(gate|up) dX (loss rows)", 3,
                                                      2 * R * I * H * 4 / 3)],
         "gemm_p8_kernel<1, 0": [("SigLIP fc1 + GELU-tanh", Lv, 2 * M_v * D * Iv)],
         "gemm_p8_kernel<0, 0, true, true|p8_fixup_kernel<0, 0>": [("SigLIP fc2 (stream-K tail + fixup)", Lv,
@@ -63,7 +63,7 @@ def roles(cfg):
         "attn_bwd_dkv256b_kernel|attn_bwd_dq256w_kernel": [("Gemma attention backward (dK / dV + dQ)", 2 * L,
                                                             attn_g / L)],
         "gemm_big_kernel<0, 0>": [("lm_head forward (+ softmax statistics)", 1, 2 * B * T * H * t.vocab_size)],
-        "gemm_p8_kernel<0, 1, false, false, 256>": [("lm_head dX (16 K slices)", 1, 2 * B * T * H * t.vocab_size)],
+        "gemm_p8_kernel<0, 1, false, false, 256": [("lm_head dX (16 K slices)", 1, 2 * B * T * H * t.vocab_size)],
     }
 
 
