@@ -465,11 +465,24 @@ size_t ptk_gemm_skinny_part_bytes(int M, int N, int K);
 int ptk_gemm_skinny(const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc, int M, int N, int K,
                     int act, void* part, size_t part_bytes, void* stream);
 
+/* The input-embedding gradient of ptk_gemma3_train_fwd_bwd (unit-test surface; the training pass calls it
+ * internally).  ids int64 [batch][text_len]; text position t of sample b is row b * seq_pad + num_vision + t of
+ * dx (fp32, `hidden` columns; seq_pad >= num_vision + text_len).  Per id, the rows' bf16(bf16(dx_row) * escale)
+ * are summed in fp32 in ascending position order, then dE[id] = bf16(dE[id] + bf16(sum)) (dE: bf16
+ * [vocab][hidden], accumulated in place; rows of ids that do not occur are not touched).  batch * text_len
+ * <= 16384 (0: nothing is done); ws: ptk_embed_grad_workspace_bytes(batch, text_len) bytes, 8-byte aligned. */
+size_t ptk_embed_grad_workspace_bytes(int batch, int text_len);
+int ptk_embed_grad(const int64_t* ids, int batch, int text_len, int num_vision, int seq_pad, int hidden, float escale,
+                   const float* dx, void* dE, void* ws, size_t ws_bytes, void* stream);
+
 /* clip_grad_norm_ + AdamW over bf16 parameters (Stage2/trainer.py:426-443, optimizer :145-149).
  * ptk_bf16_grad_scale_sumsq: g = bf16(g * scale) in place (scale 1: untouched), *out = sum g^2 (fp32,
  * deterministic; partial: >= ptk_bf16_sumsq_partial_floats() floats).  Sum the *out of every shard / rank
  * first (all-reduce), then ptk_adamw_bf16 clips by max_norm (<= 0: no clip) with that total and applies
- * AdamW with every tensor op rounded to bf16, as torch's single-tensor AdamW on bf16 parameters. */
+ * AdamW with every tensor op rounded to bf16, as torch's single-tensor AdamW on bf16 parameters.
+ * ptk_bf16_grad_scale_sumsq reads g 16 bytes at a time: g must be 16-byte aligned (a shard offset that is a
+ * multiple of 8 elements); a pointer that is not is an error before any launch.  ptk_adamw_bf16 takes any
+ * element offset; step must be >= 1. */
 int ptk_bf16_sumsq_partial_floats(void);
 int ptk_bf16_grad_scale_sumsq(void* g, int64_t n, float scale, float* partial, float* out, void* stream);
 int ptk_adamw_bf16(void* params, void* grads, void* exp_avg, void* exp_avg_sq, int64_t n, const float* sumsq_total,
@@ -480,6 +493,8 @@ int ptk_adamw_bf16(void* params, void* grads, void* exp_avg, void* exp_avg_sq, i
  * clip_grad_norm_(max_norm) + AdamW over a flat f32 parameter buffer        *
  * (Stage1/projector_trainer.py:75-79, :240-242).  grad_scale multiplies g   *
  * first (DDP 1/world).  partial: >= 1024 floats scratch.  norm_out: [1].    *
+ * grads is read as float4: it must be 16-byte aligned (checked before any   *
+ * launch; a pointer that is not is an error).                               *
  * ------------------------------------------------------------------------ */
 int ptk_clip_adamw(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n,
                    float grad_scale, float max_norm, float lr, float beta1, float beta2, float eps,

@@ -210,6 +210,9 @@ SIGNATURES = {
     "ptk_gemm_skinny_part_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ptk_gemm_skinny": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int,
                                 c_void_p, c_size_t, c_void_p]),
+    "ptk_embed_grad_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "ptk_embed_grad": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                               c_size_t, c_void_p]),
     "ptk_bf16_sumsq_partial_floats": (c_int, []),
     "ptk_bf16_grad_scale_sumsq": (c_int, [c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
     "ptk_adamw_bf16": (c_int, [c_void_p] * 4 + [c_int64, c_void_p, c_float] + [C.c_double] * 5 +

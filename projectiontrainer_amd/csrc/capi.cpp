@@ -340,6 +340,7 @@ int ptk_clip_adamw(float* params, const float* grads, float* exp_avg, float* exp
                    float max_norm, float lr, float beta1, float beta2, float eps, float weight_decay, int step,
                    float* partial, float* norm_out, void* stream) {
   if (step < 1) return set_error("clip_adamw: step must be >= 1");
+  if ((uintptr_t)grads & 15) return set_error("clip_adamw: grads must be 16-byte aligned");
   const int nparts = 1024;
   if (launch_sumsq_partial(grads, n, partial, nparts, ST)) return -1;
   return launch_clip_adamw(params, grads, exp_avg, exp_avg_sq, n, partial, nparts, grad_scale, max_norm, lr, beta1,

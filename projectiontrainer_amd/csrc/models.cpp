@@ -1174,7 +1174,26 @@ int ptk_gemma3_generate(const ptk_gemma3_config* c, const ptk_gemma3_weights* w,
 
 int ptk_bf16_sumsq_partial_floats(void) { return scale_sumsq_partial_floats(); }
 
+size_t ptk_embed_grad_workspace_bytes(int batch, int text_len) { return embed_grad_ws_bytes(batch, text_len); }
+
+int ptk_embed_grad(const int64_t* ids, int batch, int text_len, int num_vision, int seq_pad, int hidden, float escale,
+                   const float* dx, void* dE, void* ws, size_t ws_bytes, void* stream) {
+  if (batch < 0 || text_len < 0) return set_error("embed_grad: batch %d / text_len %d negative", batch, text_len);
+  const int64_t n = (int64_t)batch * text_len;
+  if (n == 0) return 0;
+  if (n > 16384) return set_error("embed_grad: %lld text tokens per batch (max 16384)", (long long)n);
+  if (!ids || !dx || !dE || !ws) return set_error("embed_grad: NULL argument");
+  if (hidden <= 0 || num_vision < 0 || seq_pad < num_vision + text_len)
+    return set_error("embed_grad: hidden %d, num_vision %d, seq_pad %d (text_len %d)", hidden, num_vision, seq_pad,
+                     text_len);
+  if (ws_bytes < embed_grad_ws_bytes(batch, text_len))
+    return set_error("embed_grad: workspace %zu bytes < %zu", ws_bytes, embed_grad_ws_bytes(batch, text_len));
+  return launch_embed_grad(ids, batch, text_len, num_vision, seq_pad, hidden, escale, dx, (bf16_t*)dE, ws,
+                           (hipStream_t)stream);
+}
+
 int ptk_bf16_grad_scale_sumsq(void* g, int64_t n, float scale, float* partial, float* out, void* stream) {
+  if ((uintptr_t)g & 15) return set_error("grad_scale_sumsq: g must be 16-byte aligned");
   return launch_scale_sumsq_bf16((bf16_t*)g, n, scale, partial, out, (hipStream_t)stream);
 }
 

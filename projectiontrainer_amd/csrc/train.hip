@@ -622,10 +622,15 @@ int launch_scale_sumsq_bf16(bf16_t* g, long n, float scale, float* partial, floa
 
 // ---------------------------------------------------------------- clip + AdamW on bf16 parameters
 // clip_grad_norm_(max_norm) on bf16 grads: total = ||g|| (fp32 sum of squares, rounded to bf16 as the
-// reference's bf16 norm tensor), coef = bf16(max_norm / bf16(total + 1e-6)) clamped to 1, g = bf16(g coef).
+// reference's bf16 norm tensor), coef = bf16(bf16(1 / bf16(total + 1e-6)) max_norm) clamped to 1 (torch's
+// `max_norm / tensor` is tensor.reciprocal() * max_norm: two roundings, the same as one only for a max_norm that
+// is a power of two), g = bf16(g coef).
 // Then torch's _single_tensor_adamw on bf16 tensors, each in-place op rounded to bf16:
-//   p = bf16(p (1 - lr wd)); m = bf16(m + (1-b1)(g - m)); v = bf16(v b2); v = bf16(v + (1-b2) g g);
-//   den = bf16(sqrt(v)); den = bf16(den / bc2s); den = bf16(den + eps); p = bf16(p - step_size m / den).
+//   p = bf16(p (1 - lr wd)); m = bf16(fma(1-b1, g - m, m)); v = bf16(v b2); v = bf16(fma((1-b2) g, g, v));
+//   den = bf16(sqrt(v)); den = bf16(den / bc2s); den = bf16(den + bf16(eps)); p = bf16(p - step_size m / den).
+// The two fused multiply-adds are torch's (lerp_ and addcmul_ on the CPU compute exactly these), written out so
+// that the result does not hang on the compiler's contraction; adding a Python scalar to a bf16 tensor rounds
+// the scalar to bf16 first.  tests/test_optim_gpu.py holds the kernel to torch's CPU result.
 __global__ void __launch_bounds__(256) adamw_bf16_kernel(bf16_t* __restrict__ p, bf16_t* __restrict__ g,
                                                          bf16_t* __restrict__ m, bf16_t* __restrict__ v, long n,
                                                          const float* __restrict__ sumsq, float max_norm,
@@ -634,9 +639,10 @@ __global__ void __launch_bounds__(256) adamw_bf16_kernel(bf16_t* __restrict__ p,
   float coef = 1.f;
   if (max_norm > 0.f) {
     const float total = bfround(sqrtf(sumsq[0]));
-    coef = fminf(bfround(max_norm / bfround(total + 1e-6f)), 1.f);
+    coef = fminf(bfround(bfround(1.f / bfround(total + 1e-6f)) * max_norm), 1.f);
     if (blockIdx.x == 0 && threadIdx.x == 0 && norm_out) norm_out[0] = total;
   }
+  eps = bfround(eps);
   for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
     float gi = bf2f(g[i]);
     if (coef != 1.f) {
@@ -645,9 +651,9 @@ __global__ void __launch_bounds__(256) adamw_bf16_kernel(bf16_t* __restrict__ p,
     }
     float pi = bfround(bf2f(p[i]) * decay);
     const float mo = bf2f(m[i]);
-    const float mi = bfround(mo + b1c * (gi - mo));
+    const float mi = bfround(fmaf(b1c, gi - mo, mo));
     float vi = bfround(bf2f(v[i]) * b2);
-    vi = bfround(vi + b2c * gi * gi);
+    vi = bfround(fmaf(b2c * gi, gi, vi));
     float den = bfround(sqrtf(vi));
     den = bfround(den / bc2s);
     den = bfround(den + eps);
