@@ -90,7 +90,23 @@ typedef struct {
    * B that stays the same from call to call (a frozen weight).  The persistent 4- / 8-wave kernels stream their B
    * pieces from it at batch 1; every other kernel family and launch shape reads B.  The result is bit-identical. */
   const void* B_kt;
+  /* k-step-tiled activations: the same layout (ptk_kstep_tile_offset(row, k, width)) over an activation [M][width],
+   * M % 16 == 0, width % 32 == 0, packed (leading dimension == width), identity row map, batch 1.  A_kt != 0: A
+   * holds the tiled form (the persistent 8-wave kernel with the plain bf16 epilogue and a B_kt).  C_kt / aux_kt /
+   * aux_in_kt != 0: the epilogue writes C / writes aux, aux2 / reads aux_in, aux_in2 in the tiled form.  These are
+   * part of the operands' contract: a launch that cannot honour one fails with an error, it never falls back to
+   * the row-major form.  ptk_gemm_ktiled_counts: launches that read a tiled A / wrote a tiled C, for tests. */
+  int A_kt, C_kt, aux_kt, aux_in_kt;
 } ptk_gemm_desc;
+int ptk_gemm_ktiled_counts(int64_t* out2, int reset);
+/* For tests (no device call): would the model-level calls run this producer / consumer pair with the producer's output
+ * k-step-tiled?  producer: a PTK_ACT_GEGLU or PTK_ACT_GEGLU_BWD GEMM, consumer: the plain bf16 GEMM that reads its C
+ * as A, both as they would be launched with the *_kt flags unset; part_floats: the split-K scratch the consumer is
+ * offered; train != 0: Stage 2 (always no).  Uses the current force mode and the PTK_A_KTILED switch (0: always no;
+ * read once, ptk_a_ktiled_reload reads it again).  Returns 1 (yes, with the GEGLU factors tiled too), 0 (no). */
+int ptk_gemm_ktiled_pair(const ptk_gemm_desc* producer, const ptk_gemm_desc* consumer, int ncu, int64_t part_floats,
+                         int train);
+int ptk_a_ktiled_reload(void);
 int ptk_gemm(const ptk_gemm_desc* d, void* stream);
 /* The k-step-tiled copy of a packed row-major bf16 matrix B[N][K] (N % 16 == 0, K % 32 == 0), of the same byte
  * size: the 1-KiB block (g, s) at byte (g * (K / 32) + s) * 1024 holds rows 16g .. 16g + 15 of k elements 32s ..

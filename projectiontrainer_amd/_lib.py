@@ -34,7 +34,8 @@ class GemmDesc(C.Structure):
                 ("aux", c_void_p), ("aux2", c_void_p), ("ld_aux", c_int64),
                 ("aux_in", c_void_p), ("aux_in2", c_void_p), ("ld_aux_in", c_int64),
                 ("amap", RowMap), ("cmap", RowMap), ("resid16", c_void_p), ("ld_resid16", c_int64),
-                ("bf16_linear", c_int), ("tail_ws", c_void_p), ("B_kt", c_void_p)]
+                ("bf16_linear", c_int), ("tail_ws", c_void_p), ("B_kt", c_void_p),
+                ("A_kt", c_int), ("C_kt", c_int), ("aux_kt", c_int), ("aux_in_kt", c_int)]
 
 
 class FlashDesc(C.Structure):
@@ -170,6 +171,9 @@ SIGNATURES = {
     "ptk_gemm_force_small_tiles": (c_int, [c_int]),
     "ptk_gemm_timer_read": (c_int, [c_int, C.POINTER(C.c_double), C.POINTER(c_int)]),
     "ptk_gemm_path_counts": (c_int, [c_void_p, c_int]),
+    "ptk_gemm_ktiled_counts": (c_int, [c_void_p, c_int]),
+    "ptk_gemm_ktiled_pair": (c_int, [C.POINTER(GemmDesc), C.POINTER(GemmDesc), c_int, c_int64, c_int]),
+    "ptk_a_ktiled_reload": (c_int, []),
     "ptk_stage_timers_enable": (c_int, [c_int]),
     "ptk_stage_begin": (c_int, [C.c_char_p, c_void_p]),
     "ptk_stage_end": (c_int, [c_void_p]),
@@ -278,6 +282,13 @@ def gemm_path_counts(reset=False):
     buf = (C.c_int64 * (8 * len(GEMM_PATHS)))()
     check(lib().ptk_gemm_path_counts(buf, int(reset)), "gemm_path_counts")
     return {(GEMM_PATHS[i // 8], i % 8): int(v) for i, v in enumerate(buf) if v}
+
+
+def gemm_ktiled_counts(reset=False):
+    """(launches that read a k-step-tiled A, launches that wrote a k-step-tiled C) since the last reset."""
+    buf = (C.c_int64 * 2)()
+    check(lib().ptk_gemm_ktiled_counts(buf, int(reset)), "gemm_ktiled_counts")
+    return int(buf[0]), int(buf[1])
 
 
 _stages_on = os.environ.get("PTK_STAGE_TIMERS", "0") not in ("", "0")

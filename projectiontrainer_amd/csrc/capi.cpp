@@ -36,6 +36,7 @@ GemmArgs to_args(const ptk_gemm_desc* d) {
   a.resid16 = (const bf16_t*)d->resid16; a.ld_resid16 = d->ld_resid16; a.bf16_linear = d->bf16_linear;
   a.tail_ws = d->tail_ws;
   a.B_kt = (const bf16_t*)d->B_kt;
+  a.a_kt = d->A_kt; a.c_kt = d->C_kt; a.aux_kt = d->aux_kt; a.aux_in_kt = d->aux_in_kt;
   return a;
 }
 
@@ -184,6 +185,13 @@ int ptk_gemm_timer_enable(int on) {
 }
 int ptk_gemm_timer_read(int act_class, double* total_ms, int* count) { return timer_read(act_class, total_ms, count); }
 int ptk_gemm_path_counts(int64_t* counts, int reset) { return path_counts(counts, reset); }
+int ptk_gemm_ktiled_counts(int64_t* out2, int reset) { return ktiled_counts(out2, reset); }
+int ptk_gemm_ktiled_pair(const ptk_gemm_desc* producer, const ptk_gemm_desc* consumer, int ncu, int64_t part_floats,
+                         int train) {
+  if (!producer || !consumer || ncu <= 0 || producer->batch > 1 || consumer->batch > 1) return 0;
+  return !train && gemm_ktiled_pair(to_args(producer), producer->act, to_args(consumer), (long)part_floats,
+                                    test_plan_env(ncu), a_ktiled_mode() != 0, true) ? 1 : 0;
+}
 
 int ptk_fill_normal_bf16(void* out, int64_t n, uint64_t seed, float std, float mean, void* stream) {
   return launch_fill_normal_bf16((bf16_t*)out, n, seed, std, mean, ST);

@@ -751,6 +751,15 @@ int path_counts(int64_t* out, int reset) {
   return 0;
 }
 
+static long g_kt_count[2];
+int ktiled_counts(int64_t* out2, int reset) {
+  for (int i = 0; i < 2; ++i) {
+    if (out2) out2[i] = g_kt_count[i];
+    if (reset) g_kt_count[i] = 0;
+  }
+  return 0;
+}
+
 // one GEMM launch's census count and optional HIP event pair (live timers): count, record e0, launch, record e1
 struct GemmLaunchScope {
   hipStream_t st;
@@ -788,7 +797,14 @@ int launch_gemm(const GemmArgs& a, int act, int out, int batch, hipStream_t st, 
   if (ntile > 0x7fffffffL) return set_error("gemm: too many tiles");
   if (!gemm_act_out(act, out, [](auto, auto) {})) return set_error("gemm: unsupported (act=%d, out=%d)", act, out);
   const GemmPlan plan = planned ? *planned : gemm_plan(a, act, out, batch, gemm_plan_env());
+  // k-step-tiled activations are the operands' contract: no family but the one with the variant may run them
+  if (a.a_kt && !a_ktiled_ok(a, plan, act, out, batch, lean_epilogue_enabled()))
+    return set_error("gemm: this launch cannot read a k-step-tiled A");
+  if (!c_ktiled_ok(a, plan, act, out, batch, lean_epilogue_enabled()))
+    return set_error("gemm: this launch cannot write k-step-tiled outputs");
   GemmLaunchScope scope(plan.path, act, st);
+  g_kt_count[0] += a.a_kt != 0;
+  g_kt_count[1] += a.c_kt != 0;
   const dim3 grid_big((unsigned)((long)((a.M + BIG - 1) / BIG) * ((a.N + BIG - 1) / BIG)), 1, 1);
   switch (plan.path) {
     case GEMM_PATH_P8:

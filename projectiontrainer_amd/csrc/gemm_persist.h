@@ -194,8 +194,17 @@ PTK_DEV void w4_pair_rows(long own, bool ok, bool, long& o1, long& o2) {
 
 // row block I of the wave's tile: lane holds C[row0 + 16I + (lane&15)][col0 + 16j + 4(lane>>4) + e]
 // (one function per row block so every accumulator index is a compile-time constant)
-template <int ACT, int OUT, int I, int NJ = 8, bool AGPR = true>
+// KTO (GEGLU only): outputs written k-step-tiled (gemm_plan.cpp kstep_tile_offset over [M][N / 2]), bit 1 h (C), bit
+// 2 the factors a, b (aux, aux2).  A store of column pair pp covers h columns [col0 / 2 + 32 pp, + 32) of 16 rows:
+// one block (row group, k-step) of the tiled form, so every store instruction writes one contiguous KiB, the lane's
+// unit in it a constant (w4_kt_unit) and the block's base uniform.  Values and rounding are the row-major form's.
+PTK_DEV uint32_t w4_kt_unit(int lane) {   // byte offset in a block of row lane & 15, logical chunk 2 (q & 1) + (q >> 1)
+  const int q = lane >> 4, chunk = 2 * (q & 1) + (q >> 1);
+  return (uint32_t)(4 * (lane & 15) + (chunk ^ ((lane >> 1) & 2))) * 16u;
+}
+template <int ACT, int OUT, int I, int NJ = 8, bool AGPR = true, int KTO = 0>
 PTK_DEV void w4_rows(const GemmArgs& p, f32x4_t (&a)[NJ], long row0, long col0, int lane, char* sink) {
+  static_assert(KTO == 0 || (ACT == ACT_GEGLU && NJ == 8), "tiled outputs: the 4-wave GEGLU epilogue");
   // pin the accumulator reads to this row block (otherwise hipcc reads all 256 up front and spills); values
   // summed in VGPRs (the stream-K reducer) are pinned there instead
 #pragma unroll
@@ -273,9 +282,27 @@ PTK_DEV void w4_rows(const GemmArgs& p, f32x4_t (&a)[NJ], long row0, long col0, 
       const bool cin = 2 * hc < p.N;
       const bool rv = w.rv && cin, sv = w.cv && cin;
       bf16_t* sk = reinterpret_cast<bf16_t*>(sink);
-      if (p.aux) *reinterpret_cast<uint4*>(rv ? p.aux + w.ro_aux + hc : sk) = uint4{gp[0], gp[1], gp[2], gp[3]};
-      if (p.aux2) *reinterpret_cast<uint4*>(rv ? p.aux2 + w.ro_aux + hc : sk) = uint4{up[0], up[1], up[2], up[3]};
-      *reinterpret_cast<uint4*>(sv ? reinterpret_cast<bf16_t*>(p.C) + w.ro_c + hc : sk) = uint4{hp[0], hp[1], hp[2], hp[3]};
+      // tiled: block (row group, k-step ks) of [M][N / 2]; M % 16 == 0 and N % 64 == 0 (c_ktiled_ok) make a block
+      // wholly valid or wholly outside, so the validity is uniform
+      const long kw = p.N >> 6, ks = (col0 >> 6) + pp, grp = (row0 >> 4) + I;
+      const bool tv = row0 + 16 * I < p.M && ks < kw;
+      const uint32_t unit = w4_kt_unit(lane);
+      if constexpr (KTO & 2) {
+        char* ta = tv ? reinterpret_cast<char*>(p.aux) + ((grp * kw + ks) << 10) + unit : sink;
+        char* tb = tv ? reinterpret_cast<char*>(p.aux2) + ((grp * kw + ks) << 10) + unit : sink;
+        *reinterpret_cast<uint4*>(ta) = uint4{gp[0], gp[1], gp[2], gp[3]};
+        *reinterpret_cast<uint4*>(tb) = uint4{up[0], up[1], up[2], up[3]};
+      } else {
+        if (p.aux) *reinterpret_cast<uint4*>(rv ? p.aux + w.ro_aux + hc : sk) = uint4{gp[0], gp[1], gp[2], gp[3]};
+        if (p.aux2) *reinterpret_cast<uint4*>(rv ? p.aux2 + w.ro_aux + hc : sk) = uint4{up[0], up[1], up[2], up[3]};
+      }
+      if constexpr (KTO & 1) {
+        const long gc = grp + (p.cmap.off >> 4);
+        char* tc = tv ? reinterpret_cast<char*>(p.C) + ((gc * kw + ks) << 10) + unit : sink;
+        *reinterpret_cast<uint4*>(tc) = uint4{hp[0], hp[1], hp[2], hp[3]};
+      } else {
+        *reinterpret_cast<uint4*>(sv ? reinterpret_cast<bf16_t*>(p.C) + w.ro_c + hc : sk) = uint4{hp[0], hp[1], hp[2], hp[3]};
+      }
     }
   } else {
     const W4Row w = w4_row(p, r);
@@ -504,17 +531,28 @@ PTK_DEV void w4_epilogue_lean(const GemmArgs& p, f32x4_t (&acc)[8][NJ], long row
 struct LeanGbwd {
   __amdgpu_buffer_rsrc_t rgi, rui, rc;
   uint32_t vin, ldin_bytes, vout, ldc_bytes;
+  uint32_t ncols;   // KTO: the wave's columns inside N (whole k-steps; a column pair past them is skipped)
 };
-template <int NP>
+// KTO: k-step-tiled forms (gemm_plan.cpp kstep_tile_offset), bit 1 the dg | du output over [M][2 N], bit 2 the saved
+// factors over [M][N] (the gate|up epilogue's tiled aux, aux2: the same lane <-> (row, columns) map, w4_kt_unit).  A
+// row group's blocks span what its 16 rows span in the row-major form (16 ld bytes), a column pair is one k-step of
+// the factors (1 KiB on) and two of the output.  Output: lane row q holds dg and du of 8 dh columns, i.e. chunk
+// q >> 1 (dg) and 2 + (q >> 1) (du) of output k-step 2 pp + (q & 1); one v_permlane16_swap of the even rows' du with
+// the odd rows' dg leaves one register with all four chunks of k-step 2 pp and the other with those of 2 pp + 1, both
+// at the lane's unit of w4_kt_unit: every store is one whole block, with no row-pair exchange (w4_line_pair).  A
+// column pair at or past N (N % 32 == 0 suffices here, not the row-major form's whole 128-column wave ranges) would
+// fall into the next row group's blocks: its loads and stores get an offset past every buffer's range instead
+template <int NP, int KTO>
 PTK_DEV void w4_gbwd_load_lean(const LeanGbwd& e, int I, u16x8_t (&G)[NP], u16x8_t (&U)[NP]) {
 #pragma unroll
   for (int pp = 0; pp < NP; ++pp) {
-    const uint32_t o = e.vin + (uint32_t)(16 * I) * e.ldin_bytes + 64u * pp;
+    uint32_t o = e.vin + (uint32_t)(16 * I) * e.ldin_bytes + ((KTO & 2) ? 1024u : 64u) * pp;
+    if constexpr (KTO != 0) o = 32u * pp < e.ncols ? o : W4_OOB;
     G[pp] = __builtin_bit_cast(u16x8_t, __builtin_amdgcn_raw_buffer_load_b128(e.rgi, o, 0, 0));
     U[pp] = __builtin_bit_cast(u16x8_t, __builtin_amdgcn_raw_buffer_load_b128(e.rui, o, 0, 0));
   }
 }
-template <int NP>
+template <int NP, int KTO>
 PTK_DEV void w4_gbwd_rows_lean(f32x4_t (&a)[2 * NP], const LeanGbwd& e, int I, const u16x8_t (&G)[NP],
                                const u16x8_t (&U)[NP]) {
 #pragma unroll
@@ -536,6 +574,19 @@ PTK_DEV void w4_gbwd_rows_lean(f32x4_t (&a)[2 * NP], const LeanGbwd& e, int I, c
       du[k] = bb.x;
       du[k + 1] = bb.y;
     }
+    if constexpr (KTO & 1) {
+      u32x4v_t x = __builtin_bit_cast(u32x4v_t, w4_pack8(dg)), y = __builtin_bit_cast(u32x4v_t, w4_pack8(du));
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {   // rows 1, 3 of x (dg) <-> rows 0, 2 of y (du)
+        const auto r = __builtin_amdgcn_permlane16_swap(x[k], y[k], false, false);
+        x[k] = r[0];
+        y[k] = r[1];
+      }
+      const uint32_t o1 = 32u * pp < e.ncols ? e.vout + (uint32_t)(16 * I) * e.ldc_bytes + 2048u * pp : W4_OOB;
+      __builtin_amdgcn_raw_buffer_store_b128(x, e.rc, o1, 0, 0);
+      __builtin_amdgcn_raw_buffer_store_b128(y, e.rc, o1 + 1024u, 0, 0);
+      continue;
+    }
     uint4 d1, d2;
     w4_line_pair(w4_pack8(dg), w4_pack8(du), false, d1, d2);
     const uint32_t o1 = e.vout + (uint32_t)(16 * I) * e.ldc_bytes + 128u * pp;
@@ -546,7 +597,7 @@ PTK_DEV void w4_gbwd_rows_lean(f32x4_t (&a)[2 * NP], const LeanGbwd& e, int I, c
 // (a lean gate|up GEGLU epilogue -- the same buffer-resource addressing for its g, u, h register-layout stores --
 // measured 1 % slower than w4_rows' on the 4-wave kernel, 762.7 vs 755.7 us, profiles/r05_lean_epilogue_ab.txt, and
 // is not kept)
-template <int ACT, int NJ>
+template <int ACT, int NJ, int KTO = 0>
 PTK_DEV void w4_epilogue_lean_glu(const GemmArgs& p, f32x4_t (&acc)[8][NJ], long row0, long col0, int lane,
                                   uint32_t c_bytes) {
   static_assert(ACT == ACT_GEGLU_BWD, "lean GEGLU backward only");
@@ -561,29 +612,35 @@ PTK_DEV void w4_epilogue_lean_glu(const GemmArgs& p, f32x4_t (&acc)[8][NJ], long
     LeanGbwd e;
     e.ldin_bytes = __builtin_amdgcn_readfirstlane((uint32_t)p.ld_aux_in * 2u);
     e.ldc_bytes = ldc_bytes;
+    e.ncols = __builtin_amdgcn_readfirstlane((uint32_t)(p.N - col0));
     e.rgi = __builtin_amdgcn_make_buffer_rsrc((void*)p.aux_in, 0, (int)(rows * e.ldin_bytes), 0x00020000);
     e.rui = __builtin_amdgcn_make_buffer_rsrc((void*)p.aux_in2, 0, (int)(rows * e.ldin_bytes), 0x00020000);
     e.rc = __builtin_amdgcn_make_buffer_rsrc(p.C, 0, (int)c_bytes, 0x00020000);
     e.vin = ((uint32_t)row0 + (lane & 15)) * e.ldin_bytes + (uint32_t)(col0 + cb) * 2u;
+    // tiled factors (ld_aux_in == N, row0 % 16 == 0, col0 % 32 == 0): group row0 / 16 starts at byte row0 x ld
+    // bytes, its k-step col0 / 32 another col0 x 32 bytes on
+    if constexpr (KTO & 2) e.vin = (uint32_t)row0 * e.ldin_bytes + (uint32_t)col0 * 32u + w4_kt_unit(lane);
     // dg | du line pp of rows (lane & 7) / 8 + (lane & 7): w4_gbwd_rows' output column map
     const bool lo = (lane & 8) == 0;
     e.vout = (crow0 + (lane & 7)) * ldc_bytes +
              (uint32_t)(2 * col0 + 8 * (4 * (cb >> 4) + ((cb >> 3) & 1) + (lo ? 0 : 2))) * 2u;
+    // tiled output (ldc == 2 N, a 16-aligned row offset): output k-step 2 col0 / 32 of group crow0 / 16
+    if constexpr (KTO & 1) e.vout = crow0 * ldc_bytes + (uint32_t)col0 * 64u + w4_kt_unit(lane);
     // the saved g, u of row block i + D load while row block i computes (D row blocks in flight)
     constexpr int D = PTK_GBWD_AHEAD;
     u16x8_t G[D][NP], U[D][NP];
 #pragma unroll
-    for (int i = 0; i < D; ++i) w4_gbwd_load_lean<NP>(e, i, G[i], U[i]);
+    for (int i = 0; i < D; ++i) w4_gbwd_load_lean<NP, KTO>(e, i, G[i], U[i]);
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
-      w4_gbwd_rows_lean<NP>(acc[i], e, i, G[i % D], U[i % D]);
-      if (i + D < 8) w4_gbwd_load_lean<NP>(e, i + D, G[i % D], U[i % D]);
+      w4_gbwd_rows_lean<NP, KTO>(acc[i], e, i, G[i % D], U[i % D]);
+      if (i + D < 8) w4_gbwd_load_lean<NP, KTO>(e, i + D, G[i % D], U[i % D]);
     }
   }
 }
 
 // the wave's 128 x 16NJ accumulator tile (8 row blocks of NJ 16x16 MFMA tiles)
-template <int ACT, int OUT, int NJ = 8, int RB = 8>
+template <int ACT, int OUT, int NJ = 8, int RB = 8, int KTO = 0>
 PTK_DEV void w4_epilogue(const GemmArgs& p, f32x4_t (&acc)[8][NJ], long row0, long col0, int lane) {
   char* sink = g_w4_sink + lane * 64;
   static_assert(RB == 8 || ACT != ACT_GEGLU_BWD, "the GEGLU backward epilogue runs 8 row blocks");
@@ -608,14 +665,14 @@ PTK_DEV void w4_epilogue(const GemmArgs& p, f32x4_t (&acc)[8][NJ], long row0, lo
     w4_gbwd_rows<7, NP>(p, acc[7], row0, col0, lane, sink, G1, U1);
     return;
   }
-  w4_rows<ACT, OUT, 0, NJ>(p, acc[0], row0, col0, lane, sink);
-  w4_rows<ACT, OUT, 1, NJ>(p, acc[1], row0, col0, lane, sink);
-  w4_rows<ACT, OUT, 2, NJ>(p, acc[2], row0, col0, lane, sink);
-  w4_rows<ACT, OUT, 3, NJ>(p, acc[3], row0, col0, lane, sink);
-  w4_rows<ACT, OUT, 4, NJ>(p, acc[4], row0, col0, lane, sink);
-  if constexpr (RB > 5) w4_rows<ACT, OUT, 5, NJ>(p, acc[5], row0, col0, lane, sink);
-  if constexpr (RB > 6) w4_rows<ACT, OUT, 6, NJ>(p, acc[6], row0, col0, lane, sink);
-  if constexpr (RB > 7) w4_rows<ACT, OUT, 7, NJ>(p, acc[7], row0, col0, lane, sink);
+  w4_rows<ACT, OUT, 0, NJ, true, KTO>(p, acc[0], row0, col0, lane, sink);
+  w4_rows<ACT, OUT, 1, NJ, true, KTO>(p, acc[1], row0, col0, lane, sink);
+  w4_rows<ACT, OUT, 2, NJ, true, KTO>(p, acc[2], row0, col0, lane, sink);
+  w4_rows<ACT, OUT, 3, NJ, true, KTO>(p, acc[3], row0, col0, lane, sink);
+  w4_rows<ACT, OUT, 4, NJ, true, KTO>(p, acc[4], row0, col0, lane, sink);
+  if constexpr (RB > 5) w4_rows<ACT, OUT, 5, NJ, true, KTO>(p, acc[5], row0, col0, lane, sink);
+  if constexpr (RB > 6) w4_rows<ACT, OUT, 6, NJ, true, KTO>(p, acc[6], row0, col0, lane, sink);
+  if constexpr (RB > 7) w4_rows<ACT, OUT, 7, NJ, true, KTO>(p, acc[7], row0, col0, lane, sink);
 }
 
 // the kernel's own GemmArgs argument (offset 0 of the kernarg segment) behind a pointer the compiler cannot

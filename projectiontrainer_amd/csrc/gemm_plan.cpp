@@ -49,11 +49,13 @@ double w4_round_fill(long M, long N, int ncu) {
 // (PTK_LEAN_EPI=0 in A/B builds, PTK_AB) keeps the general epilogue (bit-identical either way)
 // the lean GEGLU-backward epilogue (w4_epilogue_lean_glu): the saved g, u inputs with 16-B rows, no other epilogue
 // input, an offset C row map, whole 128-column wave ranges, extents below 2^31 bytes
-static bool lean_glu_ok(const GemmArgs& a, int act, int out, uint32_t& c_bytes, bool lean_epi) {
+// (kt: its k-step-tiled form, which skips a wave's column pairs past N one by one: whole k-steps of N suffice)
+static bool lean_glu_ok(const GemmArgs& a, int act, int out, uint32_t& c_bytes, bool lean_epi, bool kt = false) {
   if (!lean_epi || act != ACT_GEGLU_BWD || out != OUT_BF16) return false;
   if (a.bias || a.rowadd || a.resid || a.resid16 || a.bf16_linear || a.row_stats || a.alpha != 1.f) return false;
   const bool affine = a.cmap.g == 0 || (a.cmap.skip == 0 && a.cmap.gs == a.cmap.g);
-  if (!affine || a.cmap.off < 0 || a.amap.g != 0 || a.N % 128 || a.ldc % 8 || ((uintptr_t)a.C & 15)) return false;
+  if (!affine || a.cmap.off < 0 || a.amap.g != 0 || a.N % (kt ? 32 : 128) || a.ldc % 8 || ((uintptr_t)a.C & 15))
+    return false;
   if (!a.aux_in || !a.aux_in2 || a.ld_aux_in % 8 || a.ld_aux_in < a.N) return false;
   if (((uintptr_t)a.aux_in | (uintptr_t)a.aux_in2) & 15) return false;
   if (a.ldc < 2 * a.N) return false;
@@ -64,7 +66,7 @@ static bool lean_glu_ok(const GemmArgs& a, int act, int out, uint32_t& c_bytes, 
   return true;
 }
 bool lean_epilogue_ok(const GemmArgs& a, int act, int out, uint32_t& c_bytes, bool lean_epi) {
-  if (act == ACT_GEGLU_BWD) return lean_glu_ok(a, act, out, c_bytes, lean_epi);
+  if (act == ACT_GEGLU_BWD) return lean_glu_ok(a, act, out, c_bytes, lean_epi, a.c_kt != 0);
   if (!lean_epi || (act != ACT_NONE && act != ACT_GELU_TANH) || out != OUT_BF16) return false;
   if (a.rowadd || a.resid || a.aux || a.aux2 || a.aux_in || a.aux_in2 || a.row_stats || a.alpha != 1.f) return false;
   const bool affine = a.cmap.g == 0 || (a.cmap.skip == 0 && a.cmap.gs == a.cmap.g);
@@ -296,6 +298,57 @@ bool b_ktiled_ok(const GemmArgs& a, const GemmPlan& plan, int act, int batch) {
   if (!a.B_kt || batch != 1 || !bkt_act(act)) return false;
   if (plan.path != GEMM_PATH_W4 && plan.path != GEMM_PATH_P8 && plan.path != GEMM_PATH_P8SK) return false;
   return a.ldb == a.K && a.K % 32 == 0 && a.N % 16 == 0 && !((uintptr_t)a.B_kt & 15);
+}
+
+// The activation form: the same layout over A [M][K].  Only the 8-wave kernel has the variant (gemm_w4.hip AKT), on
+// whole tiles (no stream-K tail: a cut tail's kernel has none) with a plain bf16 epilogue and a tiled B.  A
+// tile's first 16-row group must start where its first row does: M % 16 == 0 makes every group wholly valid or
+// wholly past the buffer's end (reads zero), every tile height is a multiple of 16, and the row offset must be one
+bool a_ktiled_ok(const GemmArgs& a, const GemmPlan& plan, int act, int out, int batch, bool lean_epi) {
+  if (batch != 1 || act != ACT_NONE || out != OUT_BF16 || plan.path != GEMM_PATH_P8 || plan.tail.units) return false;
+  if (a.M % 16 || a.K % 32 || a.lda != a.K || a.amap.g != 0 || a.amap.off < 0 || a.amap.off % 16) return false;
+  (void)lean_epi;   // (the lean and the general plain bf16 epilogues both have the variant)
+  return b_ktiled_ok(a, plan, act, batch);
+}
+
+// The producers: the 4-wave kernel's GEGLU epilogue (h [M][N / 2], with aux_kt the factors a, b beside it) and its
+// lean GEGLU-backward epilogue (dg | du [M][2 N], with aux_in_kt the factors read tiled), each with a tiled B.  A
+// tiled width of whole k-steps, packed outputs, an identity C row map with a 16-aligned offset
+bool c_ktiled_ok(const GemmArgs& a, const GemmPlan& plan, int act, int out, int batch, bool lean_epi) {
+  if (!a.c_kt) return !a.aux_kt && !a.aux_in_kt;   // (the factors go tiled only beside a tiled output)
+  if (batch != 1 || out != OUT_BF16 || plan.path != GEMM_PATH_W4 || a.M % 16 || !b_ktiled_ok(a, plan, act, batch))
+    return false;
+  if (a.cmap.g != 0 || a.cmap.off < 0 || a.cmap.off % 16 || ((uintptr_t)a.C & 15)) return false;
+  if (act == ACT_GEGLU) {
+    if (a.N % 64 || a.ldc != a.N / 2 || a.aux_in_kt) return false;
+    return !a.aux_kt || (a.aux && a.aux2 && a.ld_aux == a.N / 2 && !(((uintptr_t)a.aux | (uintptr_t)a.aux2) & 15));
+  }
+  uint32_t cb = 0;
+  if (act != ACT_GEGLU_BWD || a.aux_kt || !lean_epilogue_ok(a, act, out, cb, lean_epi)) return false;
+  return a.ldc == 2L * a.N && (!a.aux_in_kt || a.ld_aux_in == a.N);
+}
+
+// One decision per producer / consumer pair, made before the producer is launched (the consumer is planned later, and
+// through gemm_split): the producer writes its output tiled (and the GEGLU factors with `factors`) and the consumer
+// reads it as a tiled A only if the producer's plan is the 4-wave kernel with that epilogue, gemm_split_plan leaves
+// the consumer unsplit and without a lent tail, the consumer's plan (the split plan's direct one; under a force mode
+// the launch plans again, so that plan) has the tiled-A variant, and both sets of operands qualify.  prod / cons:
+// the operands as they will be launched, flags unset.  enabled: the run-time switch (PTK_A_KTILED)
+bool gemm_ktiled_pair(const GemmArgs& prod, int pact, const GemmArgs& cons, long part_floats, const GemmPlanEnv& env,
+                      bool enabled, bool factors) {
+  if (!enabled || (pact != ACT_GEGLU && pact != ACT_GEGLU_BWD)) return false;
+  GemmArgs p = prod, c = cons;
+  p.c_kt = 1;
+  if (factors) (pact == ACT_GEGLU ? p.aux_kt : p.aux_in_kt) = 1;
+  c.a_kt = 1;
+  if (!c_ktiled_ok(p, gemm_plan(prod, pact, OUT_BF16, 1, env), pact, OUT_BF16, 1, env.lean_epi)) return false;
+  if (cons.A != (const bf16_t*)prod.C || cons.M != prod.M || cons.K != (pact == ACT_GEGLU ? prod.N / 2 : 2 * prod.N) ||
+      cons.amap.off != prod.cmap.off)
+    return false;
+  const GemmSplitPlan sp = gemm_split_plan(cons, OUT_BF16, part_floats, env);
+  if (sp.kc != 0 || sp.tail_ws) return false;
+  const GemmPlan cp = env.force_tiles == 0 ? sp.direct : gemm_plan(cons, ACT_NONE, OUT_BF16, 1, env);
+  return a_ktiled_ok(c, cp, ACT_NONE, OUT_BF16, 1, env.lean_epi);
 }
 
 // ============================================================================ gemm_split's rule

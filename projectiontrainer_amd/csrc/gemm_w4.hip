@@ -50,7 +50,9 @@ namespace ptk {
 
 // BKT: B is streamed from its k-step-tiled copy p.B_kt (a compile-time form: the stride of the B stream as one more
 // live scalar costs the 8-wave kernels SGPR spills, tests/test_asm_hazards.py)
-template <int ACT, int OUT, bool LEAN = false, bool BKT = false>
+// KTO: the GEGLU / lean GEGLU-backward epilogue writes (bit 1) its output and writes / reads (bit 2) the saved factors
+// k-step-tiled (gemm_persist.h w4_rows, w4_epilogue_lean_glu), for the 8-wave kernel that reads the output as its A
+template <int ACT, int OUT, bool LEAN = false, bool BKT = false, int KTO = 0>
 __global__ void __launch_bounds__(256, 1) gemm_w4_kernel(GemmArgs p, uint32_t a_bytes, uint32_t b_bytes,
                                                          uint32_t c_bytes) {
   __shared__ __attribute__((aligned(16))) char smem[W4_NSLOT * W4_SLOT];   // 160 KiB: the k-step ring
@@ -256,9 +258,9 @@ __global__ void __launch_bounds__(256, 1) gemm_w4_kernel(GemmArgs p, uint32_t a_
       {
         const long row0 = (long)bm * W4 + wr * 128, col0 = (long)bn * W4 + wc * 128;
         if constexpr (LEAN && ACT == ACT_GEGLU_BWD)
-          w4_epilogue_lean_glu<ACT, 8>(kernarg_args(), acc, row0, col0, lane, c_bytes);
+          w4_epilogue_lean_glu<ACT, 8, KTO>(kernarg_args(), acc, row0, col0, lane, c_bytes);
         else if constexpr (LEAN) w4_epilogue_lean<ACT, 8>(kernarg_args(), acc, row0, col0, lane, c_bytes);
-        else w4_epilogue<ACT, OUT>(kernarg_args(), acc, row0, col0, lane);
+        else w4_epilogue<ACT, OUT, 8, 8, KTO>(kernarg_args(), acc, row0, col0, lane);
       }
       P8_STAMP(3, (t - loc) / G);
       t += G;
@@ -286,6 +288,17 @@ bool lean_epilogue_enabled() { return PTK_AB("PTK_LEAN_EPI", 1) != 0; }
 // where b_ktiled_ok holds, which includes bkt_act: the GELU-erf epilogues have no tiled variant).
 template <int ACT, int OUT, bool LEAN>
 static void w4_launch(const GemmArgs& a, long grid, hipStream_t st, uint32_t ab, uint32_t bb, uint32_t cb) {
+  // tiled outputs (launch_gemm: c_ktiled_ok): the GEGLU and the lean GEGLU-backward epilogues with a tiled B, the
+  // output alone or with the saved factors
+  if constexpr ((ACT == ACT_GEGLU && !LEAN) || (ACT == ACT_GEGLU_BWD && LEAN)) {
+    if (a.c_kt && a.B_kt) {
+      if (a.aux_kt || a.aux_in_kt)
+        hipLaunchKernelGGL((gemm_w4_kernel<ACT, OUT, LEAN, true, 3>), dim3((unsigned)grid), dim3(256), 0, st, a, ab, bb, cb);
+      else
+        hipLaunchKernelGGL((gemm_w4_kernel<ACT, OUT, LEAN, true, 1>), dim3((unsigned)grid), dim3(256), 0, st, a, ab, bb, cb);
+      return;
+    }
+  }
   if constexpr (bkt_act(ACT)) {
     if (a.B_kt) {
       hipLaunchKernelGGL((gemm_w4_kernel<ACT, OUT, LEAN, true>), dim3((unsigned)grid), dim3(256), 0, st, a, ab, bb, cb);
@@ -305,7 +318,12 @@ int launch_gemm_w4(const GemmArgs& a, int act, int out, hipStream_t st, int max_
   const uint32_t ab = (uint32_t)std::min<double>((double)arows * a.lda * 2, 2147483000.0);
   const uint32_t bb = (uint32_t)std::min<double>((double)a.N * a.ldb * 2, 2147483000.0);
   uint32_t cb = 0;
-  if (lean_epilogue_ok(a, act, out, cb, lean_epilogue_enabled())) {
+  const bool lean = lean_epilogue_ok(a, act, out, cb, lean_epilogue_enabled());
+  if (a.c_kt || a.aux_kt || a.aux_in_kt) {   // (launch_gemm checked c_ktiled_ok; a direct caller must have too)
+    if (!a.c_kt || !a.B_kt || !((act == ACT_GEGLU && !a.aux_in_kt) || (act == ACT_GEGLU_BWD && lean && !a.aux_kt)))
+      return set_error("gemm_w4: no k-step-tiled-output variant for this launch");
+  }
+  if (lean) {
 #define PTK_W4L_CASE(ACT_) \
     if (act == ACT_)       \
       w4_launch<ACT_, OUT_BF16, true>(a, grid, st, ab, bb, cb);
@@ -373,10 +391,14 @@ constexpr int P8_PIECES = 4;   // LDS-DMA pieces per wave per k-step
 // better where 256-row tiles leave a thin last round: Gemma3's N 1152 / 1024 projections at M 22 528 (440 -> 505
 // tiles of 7/8 the work on 2 rounds), N 1536 (3 rounds either way, 7/8 the work), SigLIP's q|k|v at M 18 432,
 // its fc1 on 192-row tiles (5 rounds of 256 -> 6 of 192) -- launch_gemm: p8_tile_height
-template <int ACT, int OUT, bool SK, bool LEAN = false, int TM = 256, bool BKT = false>
+// AKT: A is a k-step-tiled activation (GemmArgs::a_kt, written in that order by its producer's epilogue; the launch:
+// a_ktiled_ok), compile-time like BKT.  Address arithmetic only: the LDS image, the fragment reads and the MFMA
+// order are the row-major form's
+template <int ACT, int OUT, bool SK, bool LEAN = false, int TM = 256, bool BKT = false, bool AKT = false>
 __global__ void __launch_bounds__(512, 1) gemm_p8_kernel(GemmArgs p, uint32_t a_bytes, uint32_t b_bytes, P8Tail tl,
                                                          uint32_t c_bytes) {
   static_assert(TM == 256 || ((TM == 224 || TM == 192 || TM == 160) && !SK), "shorter tiles: whole tiles only");
+  static_assert(!AKT || !SK, "a tiled A: whole tiles only");
   constexpr int RB = TM / 32;   // 16-row blocks per wave
   __shared__ __attribute__((aligned(16))) char smem[W4_NSLOT * W4_SLOT];   // 160 KiB: the k-step ring
   const int lane = threadIdx.x & 63;
@@ -444,6 +466,9 @@ __global__ void __launch_bounds__(512, 1) gemm_p8_kernel(GemmArgs p, uint32_t a_
   // bytes reach the same LDS units, each piece as one contiguous KiB (8 whole lines) instead of 16 half lines
   constexpr bool bkt = BKT;
   constexpr uint32_t bks = BKT ? 1024u : (uint32_t)(W4_KS * 2);   // bytes a k-step advances the B stream
+  // AKT: the tiled activation's group 2w + j of the tile's rows (TM % 16 == 0, amap.off % 16 == 0, lda == K: a
+  // tile's first group starts at the byte its first row does), a k-step one KiB on; rows past M lie past the end
+  constexpr uint32_t aks = AKT ? 1024u : (uint32_t)(W4_KS * 2);   // bytes a k-step advances the A stream
   const u32x4_t rsa = w4_rsrc(p.A, a_bytes), rsb = w4_rsrc(bkt ? p.B_kt : p.B, b_bytes);
 
   // global -> LDS: wave w fills rows 32w..32w+31 of both operands (2 + 2 pieces of 16 rows x 64 B), lane i of
@@ -453,7 +478,8 @@ __global__ void __launch_bounds__(512, 1) gemm_p8_kernel(GemmArgs p, uint32_t a_
   for (int j = 0; j < 2; ++j) {
     const int lr = wave * 32 + 16 * j + (lane >> 2);
     const int lc = (lane & 3) ^ ((lane >> 3) & 2);
-    offa[j] = (uint32_t)lr * (uint32_t)p.lda * 2u + lc * 16;
+    offa[j] = AKT ? (uint32_t)(wave * 2 + j) * (uint32_t)p.K * 32u + lane * 16
+                  : (uint32_t)lr * (uint32_t)p.lda * 2u + lc * 16;
     offb[j] = bkt ? (uint32_t)(wave * 2 + j) * (uint32_t)p.K * 32u + lane * 16   // 16-row group 2w + j
                   : (uint32_t)lr * (uint32_t)p.ldb * 2u + lc * 16;
   }
@@ -469,13 +495,13 @@ __global__ void __launch_bounds__(512, 1) gemm_p8_kernel(GemmArgs p, uint32_t a_
     int bm, bn;
     w4_tile_coords(t, nbm, nbn, bm, bn);
     uint32_t kz = 0;   // K slices as row tiles (P8Tail::zslices): byte offset of slice z's K range
-    if (!SK && tl.zslices > 1) {
+    if (!SK && !AKT && tl.zslices > 1) {   // (K slices never read a tiled A: launch_gemm_p8_kslices)
       const int nbz = nbm / tl.zslices, z = bm / nbz;
       bm -= z * nbz;
       kz = (uint32_t)z * (uint32_t)p.K * 2u;
     }
     dsa = __builtin_amdgcn_readfirstlane((uint32_t)(bm * TM + (int)p.amap.off) * (uint32_t)p.lda * 2u + kz +
-                                         (uint32_t)k0 * (W4_KT * 2));
+                                         (uint32_t)k0 * (2u * aks));
     dsb = __builtin_amdgcn_readfirstlane((uint32_t)(bn * W4) * (uint32_t)p.ldb * 2u + kz + (uint32_t)k0 * (2u * bks));
     dlen = 2 * (k1 - k0);
   };
@@ -520,7 +546,7 @@ __global__ void __launch_bounds__(512, 1) gemm_p8_kernel(GemmArgs p, uint32_t a_
     constexpr int half = decltype(half_c)::value;
     const uint32_t ba = frag_a + rs, bb = frag_b + rs;
     const uint32_t da = lds_dma + ws, db = da + W4_SOPB;
-    const uint32_t sa = dsa + dks * (W4_KS * 2), sb = dsb + dks * bks;
+    const uint32_t sa = dsa + dks * aks, sb = dsb + dks * bks;
 #pragma unroll
     for (int q = 0; q < RB; ++q) {
       // n_q = RB - 2, RB, RB, RB + 1, RB + 2, .. (8 groups: 6, 8, 8, 9, 10, 10, 10, 10; each A read fewer, one less)
@@ -598,7 +624,7 @@ __global__ void __launch_bounds__(512, 1) gemm_p8_kernel(GemmArgs p, uint32_t a_
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
       const uint32_t da = lds_dma + b * W4_SLOT, db = da + W4_SOPB;
-      const uint32_t sa = dsa + dks * (W4_KS * 2), sb = dsb + dks * bks;
+      const uint32_t sa = dsa + dks * aks, sb = dsb + dks * bks;
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         if (a_dma) W4_DMA(rsa, offa[j], sa, da + j * 1024);
@@ -779,6 +805,7 @@ size_t p8_tail_scratch_bytes_models() { return streamk_models() ? p8_tail_scratc
 // (every slice's tiles share their operand panels through L2), the caller sums the partials.  Plain fp32 out,
 // M % 256 == 0 (no tile straddles two slices), byte offsets within 4 GiB.
 int launch_gemm_p8_kslices(const GemmArgs& a, int slices, hipStream_t st) {
+  if (a.a_kt || a.c_kt) return set_error("gemm_p8_kslices: K slices take no k-step-tiled activation");
   if (slices < 1 || a.M % W4 || a.K < 128 || a.K % W4_KT || a.cmap.g || a.cmap.off || a.amap.g || a.amap.off ||
       a.bias || a.rowadd || a.resid || a.resid16 || a.aux || a.row_stats)
     return set_error("gemm_p8_kslices: unsupported operands");
@@ -802,6 +829,15 @@ int launch_gemm_p8_kslices(const GemmArgs& a, int slices, hipStream_t st) {
 template <int ACT, int OUT, bool SK, bool LEAN, int TM>
 static void p8_launch(const GemmArgs& a, long grid, hipStream_t st, uint32_t ab, uint32_t bb, const P8Tail& tl,
                       uint32_t cb) {
+  // a tiled A: the plain bf16 epilogues (lean, or general where N % 64 or an epilogue input rules the lean one out)
+  // on whole tiles with a tiled B (launch_gemm: a_ktiled_ok)
+  if constexpr (ACT == ACT_NONE && OUT == OUT_BF16 && !SK) {
+    if (a.a_kt && a.B_kt) {
+      hipLaunchKernelGGL((gemm_p8_kernel<ACT, OUT, SK, LEAN, TM, true, true>), dim3((unsigned)grid), dim3(512), 0, st, a,
+                         ab, bb, tl, cb);
+      return;
+    }
+  }
   if constexpr (bkt_act(ACT)) {
     if (a.B_kt) {
       hipLaunchKernelGGL((gemm_p8_kernel<ACT, OUT, SK, LEAN, TM, true>), dim3((unsigned)grid), dim3(512), 0, st, a, ab,
@@ -841,6 +877,10 @@ static int launch_p8_short(const GemmArgs& a, int act, int out, hipStream_t st, 
 int launch_gemm_p8(const GemmArgs& a, int act, int out, hipStream_t st, const P8Tail& tl, int tm) {
   const long ncu = device_cus();
   const bool lean_epi = lean_epilogue_enabled();
+  if (a.a_kt) {   // (launch_gemm checked a_ktiled_ok; a direct caller must have too)
+    if (act != ACT_NONE || out != OUT_BF16 || tl.units || !a.B_kt)
+      return set_error("gemm_p8: no k-step-tiled-A variant for this launch");
+  }
   if (tm != 256 && !tl.units) {
     if (!(act == ACT_NONE || (act == ACT_GELU_TANH && out == OUT_BF16)))
       return set_error("gemm_p8: %d-row tiles take the plain / GELU-tanh epilogues only", tm);

@@ -114,6 +114,26 @@ static bool ce_two_pass() {
   return v != 0;
 }
 
+// PTK_A_KTILED (result-preserving, read once; ptk_a_ktiled_reload re-reads it for tests): 0 = the Gemma MLP
+// activations h and dg | du stay row-major; 2 = they go k-step-tiled between their producer and consumer GEMMs
+// (gemm_ktiled_pair) but the saved GEGLU factors stay row-major; otherwise (default) the factors go tiled too
+static int g_a_ktiled = -1;
+}  // namespace
+namespace ptk {
+int a_ktiled_mode() {
+  if (g_a_ktiled < 0) {
+    const char* e = getenv("PTK_A_KTILED");
+    g_a_ktiled = e && e[0] == '0' ? 0 : (e && e[0] == '2' ? 2 : 1);
+  }
+  return g_a_ktiled;
+}
+}  // namespace ptk
+extern "C" int ptk_a_ktiled_reload(void) {
+  g_a_ktiled = -1;
+  return a_ktiled_mode();
+}
+namespace {
+
 // B_kt: the k-step-tiled copy of a frozen weight B, if its layer struct carries one (launch_gemm decides whether the
 // launch reads it)
 GemmArgs gemm(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
@@ -282,6 +302,7 @@ GemmaWs gemma_layout(Bump& bp, const ptk_gemma3_config* c, int B, int T, int Sp,
 int gemm_split(const GemmArgs& a, int out, float* part, long part_floats, hipStream_t st) {
   const GemmPlanEnv env = gemm_plan_env();
   const GemmSplitPlan sp = gemm_split_plan(a, out, part ? part_floats : 0, env);
+  if (sp.kc != 0 && a.a_kt) return set_error("gemm_split: a K split cannot read a k-step-tiled A");
   if (sp.kc == 0) {   // unsplit: launched with the plan the decision was made on (a force mode plans again at the launch)
     GemmArgs b = a;
     GemmPlan plan = sp.direct;
@@ -518,6 +539,40 @@ int gemma_run(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, const pt
   // the targets t >= label_offset
   const RowMap lossmap{Tl, 0, Sp, Nv - 1 + lo};
 
+  // Stage 1, layers below the last: the MLP activations h and dg | du (and the saved GEGLU factors) go k-step-tiled
+  // from the epilogue that writes them to the K loop that reads them, where the pair qualifies (gemm_ktiled_pair,
+  // one decision per pair over the layers; the factors only when both pairs run tiled: the forward writes what the
+  // backward reads).  Stage 2 reads h and dg | du token-major for the weight grads and the last layer runs compact
+  // loss-row launches: both stay row-major
+  auto mlp_fwd = [&](int l, GemmArgs& g, GemmArgs& d) {
+    const ptk_gemma3_layer& L = wt->layers[l];
+    g = gemm(train ? w.L[l].xn_ff : w.xn, H, L.wgu, H, train ? w.L[l].h : w.h, I, M, 2 * I, H, L.wgu_kt);
+    g.aux = w.L[l].glu_a; g.aux2 = w.L[l].glu_b; g.ld_aux = I;
+    d = gemm(g.C, I, L.wd, I, w.L[l].dn, H, M, H, I, L.wd_kt);
+  };
+  auto mlp_bwd = [&](int l, GemmArgs& g, GemmArgs& d) {
+    const ptk_gemma3_layer& L = wt->layers[l];
+    g = gemm(w.dao, H, L.wd_t, H, w.dgu, 2 * I, M, I, H, L.wd_t_kt);
+    g.aux_in = w.L[l].glu_a; g.aux_in2 = w.L[l].glu_b; g.ld_aux_in = I;
+    d = gemm(w.dgu, 2 * I, L.wgu_t, 2 * I, w.dtmp, H, M, H, 2 * I, L.wgu_t_kt);
+  };
+  bool h_kt = false, dgu_kt = false, fac_kt = false;   // h, dg | du, the factors a, b
+  if (!train && nl > 1 && !geglu_split() && a_ktiled_mode()) {
+    const GemmPlanEnv env = gemm_plan_env();
+    h_kt = true;
+    dgu_kt = !fwd_only;
+    fac_kt = dgu_kt && a_ktiled_mode() != 2;
+    for (int l = 0; l + 1 < nl; ++l) {
+      GemmArgs gf, df, gb, db;
+      mlp_fwd(l, gf, df);
+      mlp_bwd(l, gb, db);
+      h_kt = h_kt && gemm_ktiled_pair(gf, ACT_GEGLU, df, w.sk_floats, env, true, false);
+      dgu_kt = dgu_kt && gemm_ktiled_pair(gb, ACT_GEGLU_BWD, db, w.sk_floats, env, true, false);
+      fac_kt = fac_kt && gemm_ktiled_pair(gf, ACT_GEGLU, df, w.sk_floats, env, true, true) &&
+               gemm_ktiled_pair(gb, ACT_GEGLU_BWD, db, w.sk_floats, env, true, true);
+    }
+  }
+
   // ---------------- forward
   for (int l = 0; l < nl; ++l) {
     const ptk_gemma3_layer& L = wt->layers[l];
@@ -553,10 +608,12 @@ int gemma_run(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, const pt
                                 H, eps, st));
     sq.next("gemma.fwd.mlp");
     if (l + 1 < nl) {
-      GemmArgs g = gemm(xff, H, L.wgu, H, hh, I, M, 2 * I, H, L.wgu_kt);
-      g.aux = sv.glu_a; g.aux2 = sv.glu_b; g.ld_aux = I;
+      GemmArgs g, d;
+      mlp_fwd(l, g, d);
+      g.c_kt = d.a_kt = h_kt;
+      g.aux_kt = fac_kt;
       CK(launch_gemm(g, ACT_GEGLU, OUT_BF16, 1, st));
-      CK(gemm_split(gemm(hh, I, L.wd, I, sv.dn, H, M, H, I, L.wd_kt), OUT_BF16, w.skpart, w.sk_floats, st));
+      CK(gemm_split(d, OUT_BF16, w.skpart, w.sk_floats, st));
     } else {
       // last layer: only the loss rows reach the loss, so its MLP runs on those R rows (h, glu_a, glu_b compact);
       // the other rows of dn are zero (their residual output is never read, their gradient is zero)
@@ -659,14 +716,19 @@ int gemma_run(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, const pt
         CK(launch_gemm(gemm(w.dao, H, L.wd_t, H, w.h, I, M, I, H, L.wd_t_kt), ACT_NONE, OUT_BF16, 1, st));
         CK(launch_geglu_bwd(w.h, sv.glu_a, sv.glu_b, w.dgu, M, I, st));
       } else {
-        GemmArgs g = gemm(w.dao, H, L.wd_t, H, w.dgu, 2 * I, M, I, H, L.wd_t_kt);
-        g.aux_in = sv.glu_a;
-        g.aux_in2 = sv.glu_b;
-        g.ld_aux_in = I;
+        GemmArgs g, d;
+        mlp_bwd(l, g, d);
+        g.c_kt = dgu_kt;
+        g.aux_in_kt = fac_kt;
         CK(launch_gemm(g, ACT_GEGLU_BWD, OUT_BF16, 1, st));
       }
       if (train) CK(weight_grad(w.dgu, 2 * I, ident, 2 * I, sv.xn_ff, H, ident, H, M, w.TA, w.TB, GL->wgu, w.skpart, w.sk_floats, st));
-      CK(gemm_split(gemm(w.dgu, 2 * I, L.wgu_t, 2 * I, w.dtmp, H, M, H, 2 * I, L.wgu_t_kt), OUT_BF16, w.skpart, w.sk_floats, st));
+      {
+        GemmArgs g, d;
+        mlp_bwd(l, g, d);
+        d.a_kt = dgu_kt;   // (geglu_split: never)
+        CK(gemm_split(d, OUT_BF16, w.skpart, w.sk_floats, st));
+      }
     } else {   // last layer: MLP gradient is non-zero on the loss rows only (compact h, glu_a, glu_b, dgu)
       GemmArgs g = gemm(w.dao, H, L.wd_t, H, w.h, I, R, I, H, L.wd_t_kt);
       g.amap = lossmap;

@@ -71,12 +71,18 @@ struct GemmArgs {
   // persistent 4- / 8-wave kernels stream their B pieces from it, one contiguous KiB each, when b_ktiled_ok holds;
   // every other family reads B (bit-identical either way)
   const bf16_t* B_kt = nullptr;
+  // k-step-tiled activations (the same layout, kstep_tile_offset(row, k, width) over an [M][width] matrix of the
+  // row-major form's byte size): a_kt, A holds the tiled form (a_ktiled_ok; the persistent 8-wave kernel); c_kt /
+  // aux_kt / aux_in_kt, the epilogue writes C / aux, aux2 / reads aux_in, aux_in2 in it.  Part of the operands'
+  // contract, unlike B_kt: a launch that cannot honour a flag fails, it never falls back to row-major
+  int a_kt = 0, c_kt = 0, aux_kt = 0, aux_in_kt = 0;
 };
 
 // kernel families launch_gemm dispatches to (census: path_counts, ptk_gemm_path_counts)
 enum GemmPath { GEMM_PATH_NT = 0, GEMM_PATH_BIG = 1, GEMM_PATH_BIG2 = 2, GEMM_PATH_W4 = 3, GEMM_PATH_NTB = 4,
                 GEMM_PATH_P8SK = 5, GEMM_PATH_P8 = 6, GEMM_PATH_TN = 7, GEMM_NPATH = 9 };   // (8: unused since r06)
 int path_counts(int64_t* out, int reset);   // out [GEMM_NPATH][8] launches per (path, act class)
+int ktiled_counts(int64_t* out2, int reset);   // launches that read a k-step-tiled A / wrote a k-step-tiled C
 int device_cus();   // compute units of the current device (capi.cpp: the one cache; 256 when no device answers)
 
 // the (act, out) pairs every GEMM tile family instantiates, as template arguments: f(integral_constant<int, ACT>,
@@ -145,6 +151,20 @@ GemmPlan gemm_plan(const GemmArgs& a, int act, int out, int batch, const GemmPla
 constexpr bool bkt_act(int act) { return act != ACT_GELU_ERF && act != ACT_GELU_ERF_BWD; }
 long kstep_tile_offset(long row, long k, long K);
 bool b_ktiled_ok(const GemmArgs& a, const GemmPlan& plan, int act, int batch);
+// the launch `plan` of these operands can read A in its k-step-tiled form (a.a_kt): the 8-wave kernel on whole tiles
+// with a plain bf16 epilogue and a tiled B, batch 1, M % 16 == 0, A packed (lda == K), an identity A row map
+// with a 16-aligned offset
+bool a_ktiled_ok(const GemmArgs& a, const GemmPlan& plan, int act, int out, int batch, bool lean_epi);
+// the launch can write its output (a.c_kt) and write / read the GEGLU factors (a.aux_kt / a.aux_in_kt) tiled: the
+// 4-wave kernel's GEGLU or lean GEGLU-backward epilogue with a tiled B; true when no flag is set
+bool c_ktiled_ok(const GemmArgs& a, const GemmPlan& plan, int act, int out, int batch, bool lean_epi);
+// the producer (a GEGLU / GEGLU-backward GEMM) may write its output k-step-tiled for the consumer (a plain bf16 GEMM
+// through gemm_split) to read as its A; factors: with the GEGLU factors tiled as well (gemm_plan.cpp)
+bool gemm_ktiled_pair(const GemmArgs& prod, int pact, const GemmArgs& cons, long part_floats, const GemmPlanEnv& env,
+                      bool enabled, bool factors);
+// the run-time switch PTK_A_KTILED (models.cpp; read once): 0 no tiled activations, 2 the outputs but not the GEGLU
+// factors, otherwise (default) both
+int a_ktiled_mode();
 // validate, plan (or take `planned`, a plan gemm_plan made for these operands under the current env), launch
 int launch_gemm(const GemmArgs& a, int act, int out, int batch, hipStream_t st, const GemmPlan* planned = nullptr);
 // gemm_split's decision (models.cpp launches it).  kc == 0: launch_gemm directly (tail_ws: with the split-K scratch

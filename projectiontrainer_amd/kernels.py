@@ -26,10 +26,12 @@ def gemm(A, B, *, C=None, out_dtype=torch.bfloat16, act=L.ACT_NONE, alpha=1.0, b
          resid=None, aux=None, aux2=None, aux_in=None, aux_in2=None, M=None, N=None, K=None,
          lda=None, ldb=None, ldc=None, batch=1, batch_inner=1, strides=(0, 0, 0, 0, 0, 0),
          amap=(0, 0, 0, 0), cmap=(0, 0, 0, 0), out_mode=None, resid16=None, bf16_linear=False, tail_ws=None,
-         B_kt=None):
+         B_kt=None, A_kt=False, C_kt=False, aux_kt=False, aux_in_kt=False):
     """C = epi(alpha * A . B^T) with A [M,K], B [N,K] bf16 (K-contiguous).  tail_ws: stream-K tail scratch
     (uint8 [ptk_gemm_tail_scratch_bytes], its counters zero).  B_kt: pack_kstep_tiles(B), for a B that stays the
-    same from call to call (the persistent kernels stream it; the result is bit-identical)."""
+    same from call to call (the persistent kernels stream it; the result is bit-identical).  A_kt: A holds the
+    k-step-tiled form of the activation; C_kt / aux_kt / aux_in_kt: C / aux, aux2 are written, aux_in, aux_in2 read in
+    it (ptk_gemm_desc; a launch that cannot honour one raises)."""
     _require_cuda(A, B)
     M = A.shape[-2] if M is None else M
     K = A.shape[-1] if K is None else K
@@ -66,6 +68,7 @@ def gemm(A, B, *, C=None, out_dtype=torch.bfloat16, act=L.ACT_NONE, alpha=1.0, b
     d.bf16_linear = int(bool(bf16_linear))
     d.tail_ws = ptr(tail_ws)
     d.B_kt = ptr(B_kt)
+    d.A_kt, d.C_kt, d.aux_kt, d.aux_in_kt = int(bool(A_kt)), int(bool(C_kt)), int(bool(aux_kt)), int(bool(aux_in_kt))
     check(L.lib().ptk_gemm(d, L.stream_ptr(A.device)), "ptk_gemm")
     return C
 
