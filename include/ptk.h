@@ -473,6 +473,49 @@ int ptk_beam_candidates(const void* logits, int64_t ld, const float* beam_scores
                         uint64_t seed, int step, int n_cand, int64_t* tokens, int32_t* beam_idx, float* scores,
                         void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------ *
+ * Repetition penalty (transformers RepetitionPenaltyLogitsProcessor) in both decoders, as the reference's  *
+ * inference scripts pass it (Stage1/inference_stage1.py:176-186, Stage2/inference_vqa_stage2.py:271-318).  *
+ * A row's history is its own generated tokens so far (int64 [rows][history_ld], the first n_hist of each   *
+ * row; ids outside [0, vocab) are ignored); every DISTINCT history token is penalised once, in fp32:       *
+ * x < 0 ? x * p : x / p.  Sampling / greedy (GenerationMixin._sample) penalise the fp32 raw logits before  *
+ * temperature, top-k and top-p; beam search (_beam_search) penalises the log probs after log_softmax of    *
+ * the raw row, before the warpers, and renormalises nothing.  The penalised values are never rounded to    *
+ * bf16: the history tokens live in an LDS side list next to the bf16-keyed top-k selection of the rest.    *
+ * repetition_penalty must be finite and > 0; history must be present when n_hist > 0; history_ld >=        *
+ * n_hist.  repetition_penalty == 1 or n_hist == 0 launches exactly the unpenalised kernels.  Otherwise     *
+ * kk + n_hist <= 1024 (kk: the top-k the step keeps -- top_k, or vocab without top-k, when sampling;       *
+ * n_cand for a greedy beam step; 0 for greedy argmax) and vocab <= 294 912 (the history bitmap in LDS);    *
+ * a breach is an error before any launch.  A penalised call waits for its stream and returns an error if   *
+ * more than 2048 entries (ties at the top-k boundary) had to be kept for one row.                          *
+ * ------------------------------------------------------------------------ */
+/* One sampling step of ptk_gemma3_generate over given bf16 logits [batch][ld] (unit-test surface; the decode
+ * calls the same launcher): out int64 [batch].  finished int32 [batch] or NULL (no row finished): a finished row
+ * emits pad_token_id, a row that emits eos_token_id becomes finished.  ws: ptk_sample_next_token_workspace_bytes. */
+size_t ptk_sample_next_token_workspace_bytes(int batch);
+int ptk_sample_next_token(const void* logits, int64_t ld, int batch, int vocab, int do_sample, int top_k,
+                          float temperature, float top_p, uint64_t seed, int step, int64_t eos_token_id,
+                          int64_t pad_token_id, int32_t* finished, const int64_t* history, int64_t history_ld,
+                          int n_hist, float repetition_penalty, int64_t* out, void* ws, size_t ws_bytes,
+                          void* stream);
+/* ptk_beam_candidates with a history per decode row, int64 [batch * beams][history_ld] (the running hypothesis of
+ * each row after the beam re-order). */
+size_t ptk_beam_candidates_penalized_workspace_bytes(int batch, int beams, int n_cand);
+int ptk_beam_candidates_penalized(const void* logits, int64_t ld, const float* beam_scores, int batch, int beams,
+                                  int vocab, int do_sample, int top_k, float top_p, float temperature,
+                                  int min_tokens_to_keep, uint64_t seed, int step, int n_cand,
+                                  const int64_t* history, int64_t history_ld, int n_hist, float repetition_penalty,
+                                  int64_t* tokens, int32_t* beam_idx, float* scores, void* ws, size_t ws_bytes,
+                                  void* stream);
+/* ptk_gemma3_generate with the penalty: step t's history is out_ids[:, :t], or force_ids[:, :t] under teacher
+ * forcing; step_logits still receives the raw logits. */
+size_t ptk_gemma3_generate_penalized_workspace_bytes(const ptk_gemma3_config* c, int batch, int prompt_len,
+                                                     int max_new_tokens);
+int ptk_gemma3_generate_penalized(const ptk_gemma3_config* c, const ptk_gemma3_weights* w,
+                                  const ptk_gemma3_generate_desc* g, const float* prompt_embeds,
+                                  const int64_t* force_ids, int64_t* out_ids, void* step_logits,
+                                  float repetition_penalty, void* ws, size_t ws_bytes, void* stream);
+
 /* The decode steps' skinny GEMM (unit-test surface; the decode calls it internally): C[M][N] bf16 =
  * A[M][K] . B[N][K]^T for M <= 64, N % 128 == 0, K % 32 == 0 (K >= 64), act PTK_ACT_NONE or PTK_ACT_GEGLU
  * (interleaved gate|up columns -> N / 2 output columns); part: fp32 K-split partials of

@@ -211,6 +211,18 @@ SIGNATURES = {
     "ptk_beam_candidates": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_float,
                                     c_int, c_uint64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                     c_void_p]),
+    "ptk_sample_next_token_workspace_bytes": (c_size_t, [c_int]),
+    "ptk_sample_next_token": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_int, c_float, c_float, c_uint64, c_int,
+                                      c_int64, c_int64, c_void_p, c_void_p, c_int64, c_int, c_float, c_void_p,
+                                      c_void_p, c_size_t, c_void_p]),
+    "ptk_beam_candidates_penalized_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "ptk_beam_candidates_penalized": (c_int, [c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                              c_float, c_int, c_uint64, c_int, c_int, c_void_p, c_int64, c_int,
+                                              c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "ptk_gemma3_generate_penalized_workspace_bytes": (c_size_t, [C.POINTER(Gemma3ConfigC), c_int, c_int, c_int]),
+    "ptk_gemma3_generate_penalized": (c_int, [C.POINTER(Gemma3ConfigC), C.POINTER(Gemma3WeightsC),
+                                              C.POINTER(Gemma3GenerateC), c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_float, c_void_p, c_size_t, c_void_p]),
     "ptk_gemm_skinny_part_bytes": (c_size_t, [c_int, c_int, c_int]),
     "ptk_gemm_skinny": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int,
                                 c_void_p, c_size_t, c_void_p]),

@@ -278,10 +278,8 @@ __global__ void __launch_bounds__(GS_T) gen_sample_kernel(const bf16_t* __restri
 int launch_gen_sample(const bf16_t* logits, long ld, int B, int V, int do_sample, int top_k, float temperature,
                       float top_p, uint64_t seed, int step, long eos_id, long pad_id, int32_t* finished, int64_t* out,
                       long ld_out, int64_t* next, hipStream_t st) {
-  if (do_sample && !(temperature > 0.f)) return set_error("generate: temperature must be > 0 when sampling");
-  if (do_sample && !(top_p > 0.f && top_p <= 1.f)) return set_error("generate: top_p must be in (0, 1]");
-  if (do_sample && top_p < 1.f && !(top_k > 0 && top_k <= GS_LIST / 2) && V > GS_LIST / 2)
-    return set_error("generate: top_p < 1 needs 0 < top_k <= %d (the kept set is sorted in LDS)", GS_LIST / 2);
+  if (gen_sample_validate("generate", V, do_sample, top_k, temperature, top_p, PenArgs{nullptr, 0, 0, 1.f, nullptr}))
+    return -1;
   hipLaunchKernelGGL(gen_sample_kernel, dim3((unsigned)B), dim3(GS_T), 0, st, logits, ld, V, do_sample, top_k,
                      temperature, do_sample ? top_p : 1.f, seed, step, eos_id, pad_id, finished, out, ld_out, next);
   return hipGetLastError() == hipSuccess ? 0 : set_error("gen_sample launch failed");
@@ -515,6 +513,7 @@ __global__ void __launch_bounds__(BC_T) beam_cand_kernel(const bf16_t* __restric
   __syncthreads();
   const bool bad = cnt > BC_LIST;
   const int n = min(cnt, BC_LIST);
+  __syncthreads();   // every wave has read cnt before thread 0 rewrites it below (the top-p start index)
   // top-p over the kept entries: bitonic sort ascending by score (then token), cumulative softmax
   if (do_sample && top_p < 1.f) {
     int np2 = 1;
@@ -636,14 +635,9 @@ int launch_beam_candidates(const bf16_t* logits, long ld, const float* beam_scor
                            int do_sample, int top_k, float top_p, float temperature, int min_keep, uint64_t seed,
                            int step, int n_cand, int64_t* tok, int32_t* beam, float* score, void* ws,
                            size_t ws_bytes, hipStream_t st) {
-  if (batch <= 0 || K <= 0 || K > 8 || V <= 0 || n_cand <= 0 || n_cand > 32)
-    return set_error("beam_candidates: batch %d, beams %d (1..8), vocab %d, n_cand %d (1..32)", batch, K, V, n_cand);
-  if (do_sample && !(temperature > 0.f)) return set_error("beam_candidates: temperature must be > 0 when sampling");
-  if (do_sample && !(top_p > 0.f && top_p <= 1.f)) return set_error("beam_candidates: top_p must be in (0, 1]");
-  if (do_sample && !(top_k > 0 && top_k <= BC_LIST / 2) && V > BC_LIST / 2)
-    return set_error("beam_candidates: sampling needs 0 < top_k <= %d (the kept set lives in LDS)", BC_LIST / 2);
-  if (!ws || ws_bytes < beam_candidates_ws_bytes(batch, K, n_cand))
-    return set_error("beam_candidates: workspace too small (%zu bytes needed)", beam_candidates_ws_bytes(batch, K, n_cand));
+  if (beam_candidates_validate(batch, K, V, do_sample, top_k, top_p, temperature, min_keep, n_cand, ws, ws_bytes,
+                               PenArgs{nullptr, 0, 0, 1.f, nullptr}))
+    return -1;
   const long nr = (long)batch * K * n_cand;
   float* sk = (float*)ws;
   float* sa = sk + nr;
@@ -651,6 +645,458 @@ int launch_beam_candidates(const bf16_t* logits, long ld, const float* beam_scor
   hipLaunchKernelGGL(beam_cand_kernel, dim3((unsigned)(batch * K)), dim3(BC_T), 0, st, logits, ld, beam_scores, K, V,
                      do_sample, top_k, top_p, temperature, min_keep, seed, step, n_cand, sk, sa, stok);
   if (hipGetLastError() != hipSuccess) return set_error("beam_candidates launch failed");
+  hipLaunchKernelGGL(beam_merge_kernel, dim3((unsigned)batch), dim3(64), 0, st, sk, sa, stok, K, n_cand, tok, beam,
+                     score);
+  return hipGetLastError() == hipSuccess ? 0 : set_error("beam_merge launch failed");
+}
+
+// ------------------------------------------------------------------ repetition penalty
+// transformers RepetitionPenaltyLogitsProcessor (generation/logits_process.py) in both selections above: every
+// DISTINCT token of a row's history (its own generated tokens so far) is penalised once, in fp32, x < 0 ? x * p :
+// x / p -- on the raw logits before temperature / top-k / top-p when sampling (GenerationMixin._sample), on the log
+// probs after log_softmax of the raw row in beam search (_beam_search; nothing is renormalised).  A penalised value
+// is not a bf16, so it cannot pass through the 16-bit key selection: the history tokens of a row become a side
+// list in LDS (token, raw bits), a V-bit LDS bitmap keeps them out of the bf16-keyed passes (their keys are
+// subtracted from the radix histograms, and they are skipped where the passes collect), and the side list joins
+// the kept list with its fp32 penalised scores.  The kept set is then the kk largest (ties kept) of that union,
+// selected in fp32 on the sorted LDS list: with p > 1 history tokens leave the top set, with p < 1 up to n_hist
+// of them enter it.  p == 1 or an empty history never comes here (the launchers call the kernels above).
+constexpr int PEN_T = 1024;        // threads per row (>= PEN_CAP: one thread per history token)
+constexpr int PEN_CAP = 1024;      // kk + n_hist at most (checked on the host before the launch)
+constexpr int PEN_LIST = 2048;     // kept entries per row: PEN_CAP and the ties at the top-k boundary
+constexpr int PEN_VMAX = 294912;   // vocab at most: the bitmap takes V / 8 bytes of LDS (36 KiB here)
+
+PTK_DEV float pen_apply(float x, float p) { return x < 0.f ? x * p : x / p; }
+PTK_DEV bool pen_member(const uint32_t* bm, int i) { return (bm[i >> 5] >> (i & 31)) & 1u; }
+
+// the row's side list: h_tok[j] = the j-th history token where it is the first of its value to arrive (else -1:
+// a repeat, or an id outside [0, V)), h_bits[j] its raw logit; bm: one bit per vocabulary entry, set for those
+__device__ void pen_side_list(const int64_t* __restrict__ h, int n_hist, const uint16_t* row, int V, uint32_t* bm,
+                              int* h_tok, uint16_t* h_bits) {
+  const int tid = threadIdx.x;
+  for (int i = tid; i < (V + 31) / 32; i += PEN_T) bm[i] = 0;
+  __syncthreads();
+  if (tid < n_hist) {
+    const long t = h[tid];
+    int keep = -1;
+    uint16_t u = 0;
+    if (t >= 0 && t < V) {
+      const uint32_t bit = 1u << (t & 31);
+      if (!(atomicOr(&bm[t >> 5], bit) & bit)) { keep = (int)t; u = row[t]; }
+    }
+    h_tok[tid] = keep;
+    h_bits[tid] = u;
+  }
+  __syncthreads();
+}
+
+// key of the kk-th largest raw logit among the entries outside the side list (two-pass radix select as above; the
+// side list's keys leave each histogram again); fewer than kk such entries: 0 (all of them)
+__device__ uint32_t pen_threshold(const uint16_t* row, int V, int kk, int n_hist, const int* h_tok,
+                                  const uint16_t* h_bits, uint32_t* hist, uint32_t* sel) {
+  const int tid = threadIdx.x;
+  uint32_t need = (uint32_t)kk, hi = 0, thr = 0;
+  for (int pass = 0; pass < 2; ++pass) {
+    for (int i = tid; i < 256; i += PEN_T) hist[i] = 0;
+    __syncthreads();
+    scan_row<PEN_T>(row, V, [&](int, uint16_t u) {
+      const uint32_t key = bf_key(u);
+      if (pass == 0) atomicAdd(&hist[key >> 8], 1u);
+      else if ((key >> 8) == hi) atomicAdd(&hist[key & 255u], 1u);
+    });
+    __syncthreads();
+    if (tid < n_hist && h_tok[tid] >= 0) {
+      const uint32_t key = bf_key(h_bits[tid]);
+      if (pass == 0) atomicSub(&hist[key >> 8], 1u);
+      else if ((key >> 8) == hi) atomicSub(&hist[key & 255u], 1u);
+    }
+    __syncthreads();
+    if (tid == 0) {
+      uint32_t acc = 0;
+      int bin = 255;
+      for (; bin > 0; --bin) {
+        if (acc + hist[bin] >= need) break;
+        acc += hist[bin];
+      }
+      sel[0] = (uint32_t)bin;
+      sel[1] = need > acc ? need - acc : 0u;
+    }
+    __syncthreads();
+    if (pass == 0) { hi = sel[0]; need = sel[1]; }
+    else thr = (hi << 8) | sel[0];
+    __syncthreads();
+  }
+  return thr;
+}
+
+// ls / lt [0, n) ascending by score, then token (bitonic; n <= PEN_LIST)
+__device__ void pen_sort(float* ls, int* lt, int n) {
+  const int tid = threadIdx.x;
+  int np2 = 1;
+  while (np2 < n) np2 <<= 1;
+  for (int i = n + tid; i < np2; i += PEN_T) { ls[i] = INFINITY; lt[i] = 0x7fffffff; }
+  __syncthreads();
+  for (int size = 2; size <= np2; size <<= 1)
+    for (int stride = size >> 1; stride > 0; stride >>= 1) {
+      for (int i = tid; i < np2; i += PEN_T) {
+        const int j = i ^ stride;
+        if (j > i) {
+          const bool up = (i & size) == 0;
+          const float a = ls[i], c = ls[j];
+          const bool gt = a > c || (a == c && lt[i] > lt[j]);
+          if (gt == up) { ls[i] = c; ls[j] = a; const int tt = lt[i]; lt[i] = lt[j]; lt[j] = tt; }
+        }
+      }
+      __syncthreads();
+    }
+}
+
+// start of the kk largest of the sorted list, ties with the kk-th kept (TopKLogitsWarper: scores < the kk-th dropped)
+PTK_DEV int pen_topk_start(const float* ls, int n, int kk) {
+  if (n <= kk) return 0;
+  int lo = n - kk;
+  const float kv = ls[lo];
+  while (lo > 0 && ls[lo - 1] == kv) --lo;
+  return lo;
+}
+
+// gen_sample_kernel with the penalty: the history of row b is history[b * ld_hist + 0 .. n_hist)
+__global__ void __launch_bounds__(PEN_T) gen_sample_pen_kernel(const bf16_t* __restrict__ logits, long ld, int V,
+                                                               int do_sample, int top_k, float temperature,
+                                                               float top_p, uint64_t seed, int step, long eos_id,
+                                                               long pad_id, int32_t* __restrict__ finished,
+                                                               int64_t* __restrict__ out, long ld_out,
+                                                               int64_t* __restrict__ next,
+                                                               const int64_t* __restrict__ history, long ld_hist,
+                                                               int n_hist, float pen, int32_t* __restrict__ status) {
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  constexpr int NW = PEN_T / 64;
+  const uint16_t* row = reinterpret_cast<const uint16_t*>(logits) + (long)b * ld;
+  extern __shared__ uint32_t pen_bm[];
+  __shared__ int h_tok[PEN_CAP];
+  __shared__ uint16_t h_bits[PEN_CAP];
+  __shared__ uint32_t hist[256];
+  __shared__ float redf[NW];
+  __shared__ int redi[NW];
+  __shared__ uint32_t sel[2];
+  __shared__ float ls[PEN_LIST];
+  __shared__ int lt[PEN_LIST];
+  __shared__ int cnt;
+  const bool fin = finished[b] != 0;
+  long tok = pad_id;
+  bool over = false;
+  if (!fin) {
+    pen_side_list(history + (long)b * ld_hist, n_hist, row, V, pen_bm, h_tok, h_bits);
+    // max (and its first index) of the penalised row: the entries outside the side list, then the side list
+    float mx = -INFINITY;
+    int mi = 0x7fffffff;
+    scan_row<PEN_T>(row, V, [&](int i, uint16_t u) {
+      const float v = bf2f(u);
+      if (v > mx && !pen_member(pen_bm, i)) { mx = v; mi = i; }
+    });
+    if (tid < n_hist && h_tok[tid] >= 0) {
+      const float v = pen_apply(bf2f(h_bits[tid]), pen);
+      if (v > mx || (v == mx && h_tok[tid] < mi)) { mx = v; mi = h_tok[tid]; }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const float ov = __shfl_xor(mx, o, 64);
+      const int oi = __shfl_xor(mi, o, 64);
+      if (ov > mx || (ov == mx && oi < mi)) { mx = ov; mi = oi; }
+    }
+    if (lane == 0) { redf[wave] = mx; redi[wave] = mi; }
+    __syncthreads();
+    mx = redf[0];
+    mi = redi[0];
+    for (int w = 1; w < NW; ++w)
+      if (redf[w] > mx || (redf[w] == mx && redi[w] < mi)) { mx = redf[w]; mi = redi[w]; }
+    __syncthreads();
+    if (!do_sample) {
+      tok = mi;
+    } else {
+      const int kk = (top_k > 0 && top_k < V) ? top_k : V;
+      const uint32_t thr = kk < V ? pen_threshold(row, V, kk, n_hist, h_tok, h_bits, hist, sel) : 0u;
+      const float inv_t = 1.f / temperature;
+      if (tid == 0) cnt = 0;
+      __syncthreads();
+      scan_row<PEN_T>(row, V, [&](int i, uint16_t u) {
+        if (bf_key(u) >= thr && !pen_member(pen_bm, i)) {
+          const int slot = atomicAdd(&cnt, 1);
+          if (slot < PEN_LIST) { ls[slot] = (bf2f(u) - mx) * inv_t; lt[slot] = i; }
+        }
+      });
+      if (tid < n_hist && h_tok[tid] >= 0) {
+        const int slot = atomicAdd(&cnt, 1);
+        if (slot < PEN_LIST) { ls[slot] = (pen_apply(bf2f(h_bits[tid]), pen) - mx) * inv_t; lt[slot] = h_tok[tid]; }
+      }
+      __syncthreads();
+      const int n = cnt;
+      over = n > PEN_LIST;
+      if (!over) {
+        pen_sort(ls, lt, n);
+        if (tid == 0) {   // (<= 2048 entries, once per row and token)
+          const int lo = pen_topk_start(ls, n, kk);
+          float tot = 0.f;
+          for (int i = lo; i < n; ++i) tot += __expf(ls[i]);   // z <= 0 (the penalised row's max at 0)
+          float cum = 0.f;
+          int first = lo;
+          for (int i = lo; i < n; ++i) {
+            cum += __expf(ls[i]);
+            if (cum / tot <= 1.f - top_p) first = i + 1;
+          }
+          first = min(first, n - 1);
+          float kept = 0.f;
+          for (int i = first; i < n; ++i) kept += __expf(ls[i]);
+          const float target = gen_uniform(seed, step, b) * kept;
+          float s = 0.f;
+          int pick = lt[n - 1];
+          for (int i = first; i < n; ++i) {
+            s += __expf(ls[i]);
+            if (target < s) { pick = lt[i]; break; }
+          }
+          redi[0] = pick;
+        }
+        __syncthreads();
+        tok = redi[0];
+      }
+    }
+  }
+  if (tid == 0) {
+    // an over-full list: the row stops with pad_id and the status word makes the host call fail
+    if (over) atomicOr(status, 1);
+    out[(long)b * ld_out] = tok;
+    next[b] = tok;
+    if (!fin && (tok == eos_id || over)) finished[b] = 1;
+  }
+}
+
+// beam_cand_kernel with the penalty: the history of decode row r is history[r * ld_hist + 0 .. n_hist)
+__global__ void __launch_bounds__(PEN_T) beam_cand_pen_kernel(const bf16_t* __restrict__ logits, long ld,
+                                                              const float* __restrict__ beam_scores, int K, int V,
+                                                              int do_sample, int top_k, float top_p,
+                                                              float temperature, int min_keep, uint64_t seed,
+                                                              int step, int n_cand, float* __restrict__ sc_key,
+                                                              float* __restrict__ sc_acc,
+                                                              int32_t* __restrict__ sc_tok,
+                                                              const int64_t* __restrict__ history, long ld_hist,
+                                                              int n_hist, float pen, int32_t* __restrict__ status) {
+  const int rowi = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  constexpr int NW = PEN_T / 64;
+  extern __shared__ uint32_t pen_bm[];
+  __shared__ int h_tok[PEN_CAP];
+  __shared__ uint16_t h_bits[PEN_CAP];
+  __shared__ uint32_t hist[256];
+  __shared__ float redf[NW];
+  __shared__ int redi[NW];
+  __shared__ uint32_t sel[2];
+  __shared__ int cnt, first_s;
+  __shared__ float ls[PEN_LIST];     // kept entries of the row: log prob (processed), then accumulated
+  __shared__ int lt[PEN_LIST];       //                              token
+  __shared__ float best_key[32], best_acc[32];
+  __shared__ int best_tok[32];
+  __shared__ int nbest;
+  if (tid == 0) nbest = 0;
+  const float inv_t = (do_sample && temperature > 0.f) ? 1.f / temperature : 1.f;
+  const uint16_t* row = reinterpret_cast<const uint16_t*>(logits) + (long)rowi * ld;
+  pen_side_list(history + (long)rowi * ld_hist, n_hist, row, V, pen_bm, h_tok, h_bits);
+  // log_softmax statistics of the RAW row (the penalty acts on the log probs)
+  float mx = -INFINITY;
+  scan_row<PEN_T>(row, V, [&](int, uint16_t u) { mx = fmaxf(mx, bf2f(u)); });
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
+  if (lane == 0) redf[wave] = mx;
+  __syncthreads();
+  mx = redf[0];
+  for (int w = 1; w < NW; ++w) mx = fmaxf(mx, redf[w]);
+  __syncthreads();
+  float se = 0.f;
+  scan_row<PEN_T>(row, V, [&](int, uint16_t u) { se += __expf(bf2f(u) - mx); });
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) se += __shfl_xor(se, o, 64);
+  if (lane == 0) redf[wave] = se;
+  __syncthreads();
+  se = 0.f;
+  for (int w = 0; w < NW; ++w) se += redf[w];
+  const float lse = mx + __logf(se);
+  __syncthreads();
+  // the kept list: the kk largest raw logits outside the side list (ties kept), and the side list penalised
+  const int kk = do_sample ? (top_k > 0 ? max(top_k, min_keep) : V) : n_cand;
+  const uint32_t thr = kk < V ? pen_threshold(row, V, kk, n_hist, h_tok, h_bits, hist, sel) : 0u;
+  if (tid == 0) cnt = 0;
+  __syncthreads();
+  scan_row<PEN_T>(row, V, [&](int i, uint16_t u) {
+    if (bf_key(u) >= thr && !pen_member(pen_bm, i)) {
+      const int slot = atomicAdd(&cnt, 1);
+      if (slot < PEN_LIST) { ls[slot] = (bf2f(u) - lse) * inv_t; lt[slot] = i; }
+    }
+  });
+  if (tid < n_hist && h_tok[tid] >= 0) {
+    const int slot = atomicAdd(&cnt, 1);
+    if (slot < PEN_LIST) { ls[slot] = pen_apply(bf2f(h_bits[tid]) - lse, pen) * inv_t; lt[slot] = h_tok[tid]; }
+  }
+  __syncthreads();
+  const bool bad = cnt > PEN_LIST;
+  const int n = min(cnt, PEN_LIST);
+  if (bad && tid == 0) atomicOr(status, 1);
+  // sampling: top-k (ties kept) of the union in fp32, then top-p, on the sorted list; greedy needs neither (the
+  // n_cand rounds below take the largest of the whole list)
+  if (do_sample) {
+    pen_sort(ls, lt, n);
+    if (tid == 0) {   // (n <= 2048 entries, once per row and step)
+      const int lo = pen_topk_start(ls, n, kk);
+      int first = lo;
+      if (top_p < 1.f) {
+        const float top = ls[n - 1];
+        float tot = 0.f;
+        for (int i = lo; i < n; ++i) tot += __expf(ls[i] - top);
+        float cum = 0.f;
+        for (int i = lo; i < n; ++i) {
+          cum += __expf(ls[i] - top);
+          if (cum / tot <= 1.f - top_p) first = i + 1;
+        }
+        first = min(first, max(lo, n - min_keep));
+      }
+      first_s = first;   // kept: [first, n)
+    }
+  } else if (tid == 0) {
+    first_s = 0;
+  }
+  __syncthreads();
+  const int first = first_s;
+  const float bs = beam_scores[rowi];
+  for (int i = first + tid; i < n; i += PEN_T) ls[i] += bs;   // accumulated = processed log prob + beam score
+  __syncthreads();
+  for (int rnd = 0; rnd < n_cand; ++rnd) {
+    float bk = -INFINITY;
+    int bi = -1;
+    for (int i = first + tid; i < n; i += PEN_T) {
+      if (lt[i] < 0) continue;   // taken
+      const float key = do_sample ? ls[i] + bc_gumbel(seed, step, rowi, lt[i]) : ls[i];
+      if (key > bk || (key == bk && (bi < 0 || lt[i] < lt[bi]))) { bk = key; bi = i; }
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const float ok = __shfl_xor(bk, o, 64);
+      const int oi = __shfl_xor(bi, o, 64);
+      if (ok > bk || (ok == bk && oi >= 0 && (bi < 0 || lt[oi] < lt[bi]))) { bk = ok; bi = oi; }
+    }
+    if (lane == 0) { redf[wave] = bk; redi[wave] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+      float k0 = redf[0];
+      int i0 = redi[0];
+      for (int w = 1; w < NW; ++w)
+        if (redf[w] > k0 || (redf[w] == k0 && redi[w] >= 0 && (i0 < 0 || lt[redi[w]] < lt[i0]))) { k0 = redf[w]; i0 = redi[w]; }
+      if (i0 >= 0 && k0 > -INFINITY) {
+        best_key[nbest] = k0; best_acc[nbest] = ls[i0]; best_tok[nbest] = lt[i0];
+        ++nbest;
+        lt[i0] = -1;
+      }
+    }
+    __syncthreads();
+  }
+  if (tid < n_cand) {
+    const long o = (long)rowi * n_cand + tid;
+    const bool ok = tid < nbest;
+    sc_key[o] = ok ? best_key[tid] : -INFINITY;
+    sc_acc[o] = ok ? best_acc[tid] : -INFINITY;
+    sc_tok[o] = bad ? -2 : (ok ? best_tok[tid] : -1);
+  }
+}
+
+int pen_validate(const char* who, const PenArgs& pa) {
+  if (!(pa.penalty > 0.f) || !std::isfinite(pa.penalty))
+    return set_error("%s: repetition_penalty must be a finite float > 0 (got %g)", who, (double)pa.penalty);
+  if (pa.n_hist < 0) return set_error("%s: n_hist %d < 0", who, pa.n_hist);
+  if (pa.n_hist > 0 && !pa.history) return set_error("%s: history is NULL with n_hist %d", who, pa.n_hist);
+  if (pa.ld_hist < pa.n_hist) return set_error("%s: history_ld %ld < n_hist %d", who, pa.ld_hist, pa.n_hist);
+  return 0;
+}
+static int pen_capacity(const char* who, int kk, int n_hist, int V) {
+  if ((long)kk + n_hist > PEN_CAP)
+    return set_error("%s: repetition_penalty keeps top-k + history in LDS: %d + %d tokens exceed the limit of %d",
+                     who, kk, n_hist, PEN_CAP);
+  if (V > PEN_VMAX) return set_error("%s: repetition_penalty needs vocab <= %d (the history bitmap in LDS)", who, PEN_VMAX);
+  return 0;
+}
+// the entries a step keeps ahead of top-p (the one definition of kk; the kernels compute the same)
+static int gen_sample_kk(int V, int do_sample, int top_k) {
+  return do_sample ? ((top_k > 0 && top_k < V) ? top_k : V) : 0;
+}
+static int beam_kk(int V, int do_sample, int top_k, int min_keep, int n_cand) {
+  return std::min(V, do_sample ? (top_k > 0 ? std::max(top_k, min_keep) : V) : n_cand);
+}
+// Every host-side rule of one sampling step / one beam selection, penalised or not, with no device call: the
+// launchers run them first, and so does an entry point that has device work of its own ahead of the launch.
+int gen_sample_validate(const char* who, int V, int do_sample, int top_k, float temperature, float top_p,
+                        const PenArgs& pa) {
+  if (pen_validate(who, pa)) return -1;
+  if (do_sample && !(temperature > 0.f)) return set_error("%s: temperature must be > 0 when sampling", who);
+  if (do_sample && !(top_p > 0.f && top_p <= 1.f)) return set_error("%s: top_p must be in (0, 1]", who);
+  if (pen_active(pa)) return pen_capacity(who, gen_sample_kk(V, do_sample, top_k), pa.n_hist, V);
+  if (do_sample && top_p < 1.f && !(top_k > 0 && top_k <= GS_LIST / 2) && V > GS_LIST / 2)
+    return set_error("%s: top_p < 1 needs 0 < top_k <= %d (the kept set is sorted in LDS)", who, GS_LIST / 2);
+  return 0;
+}
+int beam_candidates_validate(int batch, int K, int V, int do_sample, int top_k, float top_p, float temperature,
+                             int min_keep, int n_cand, const void* ws, size_t ws_bytes, const PenArgs& pa) {
+  const char* who = "beam_candidates";
+  if (pen_validate(who, pa)) return -1;
+  if (batch <= 0 || K <= 0 || K > 8 || V <= 0 || n_cand <= 0 || n_cand > 32)
+    return set_error("beam_candidates: batch %d, beams %d (1..8), vocab %d, n_cand %d (1..32)", batch, K, V, n_cand);
+  if (do_sample && !(temperature > 0.f)) return set_error("beam_candidates: temperature must be > 0 when sampling");
+  if (do_sample && !(top_p > 0.f && top_p <= 1.f)) return set_error("beam_candidates: top_p must be in (0, 1]");
+  if (pen_active(pa)) {
+    if (pen_capacity(who, beam_kk(V, do_sample, top_k, min_keep, n_cand), pa.n_hist, V)) return -1;
+  } else if (do_sample && !(top_k > 0 && top_k <= BC_LIST / 2) && V > BC_LIST / 2) {
+    return set_error("beam_candidates: sampling needs 0 < top_k <= %d (the kept set lives in LDS)", BC_LIST / 2);
+  }
+  // (a penalised call keeps its status word in the 256 bytes behind the unpenalised workspace)
+  const size_t need = beam_candidates_ws_bytes(batch, K, n_cand) + (pen_active(pa) ? 256 : 0);
+  if (!ws || ws_bytes < need) return set_error("beam_candidates: workspace too small (%zu bytes needed)", need);
+  return 0;
+}
+int pen_status_check(const char* who, int32_t* status, hipStream_t st) {
+  int32_t h = 0;
+  if (hipMemcpyAsync(&h, status, 4, hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+    return set_error("%s: reading the repetition-penalty status failed", who);
+  if (h) return set_error("%s: more than %d entries to keep for one row (ties at the top-k boundary)", who, PEN_LIST);
+  return 0;
+}
+static size_t pen_bitmap_bytes(int V) { return (size_t)((V + 31) / 32) * 4; }
+
+int launch_gen_sample_pen(const bf16_t* logits, long ld, int B, int V, int do_sample, int top_k, float temperature,
+                          float top_p, uint64_t seed, int step, long eos_id, long pad_id, int32_t* finished,
+                          int64_t* out, long ld_out, int64_t* next, const PenArgs& pa, hipStream_t st) {
+  if (gen_sample_validate("generate", V, do_sample, top_k, temperature, top_p, pa)) return -1;
+  if (!pen_active(pa))
+    return launch_gen_sample(logits, ld, B, V, do_sample, top_k, temperature, top_p, seed, step, eos_id, pad_id,
+                             finished, out, ld_out, next, st);
+  if (!pa.status) return set_error("generate: repetition_penalty needs a status word");
+  hipLaunchKernelGGL(gen_sample_pen_kernel, dim3((unsigned)B), dim3(PEN_T), pen_bitmap_bytes(V), st, logits, ld, V,
+                     do_sample, top_k, temperature, do_sample ? top_p : 1.f, seed, step, eos_id, pad_id, finished, out,
+                     ld_out, next, pa.history, pa.ld_hist, pa.n_hist, pa.penalty, pa.status);
+  return hipGetLastError() == hipSuccess ? 0 : set_error("gen_sample_pen launch failed");
+}
+
+int launch_beam_candidates_pen(const bf16_t* logits, long ld, const float* beam_scores, int batch, int K, int V,
+                               int do_sample, int top_k, float top_p, float temperature, int min_keep, uint64_t seed,
+                               int step, int n_cand, int64_t* tok, int32_t* beam, float* score, void* ws,
+                               size_t ws_bytes, const PenArgs& pa, hipStream_t st) {
+  if (beam_candidates_validate(batch, K, V, do_sample, top_k, top_p, temperature, min_keep, n_cand, ws, ws_bytes, pa))
+    return -1;
+  if (!pen_active(pa))
+    return launch_beam_candidates(logits, ld, beam_scores, batch, K, V, do_sample, top_k, top_p, temperature, min_keep,
+                                  seed, step, n_cand, tok, beam, score, ws, ws_bytes, st);
+  if (!pa.status) return set_error("beam_candidates: repetition_penalty needs a status word");
+  const long nr = (long)batch * K * n_cand;
+  float* sk = (float*)ws;
+  float* sa = sk + nr;
+  int32_t* stok = (int32_t*)(sa + nr);
+  hipLaunchKernelGGL(beam_cand_pen_kernel, dim3((unsigned)(batch * K)), dim3(PEN_T), pen_bitmap_bytes(V), st, logits,
+                     ld, beam_scores, K, V, do_sample, top_k, top_p, temperature, min_keep, seed, step, n_cand, sk, sa,
+                     stok, pa.history, pa.ld_hist, pa.n_hist, pa.penalty, pa.status);
+  if (hipGetLastError() != hipSuccess) return set_error("beam_candidates_pen launch failed");
   hipLaunchKernelGGL(beam_merge_kernel, dim3((unsigned)batch), dim3(64), 0, st, sk, sa, stok, K, n_cand, tok, beam,
                      score);
   return hipGetLastError() == hipSuccess ? 0 : set_error("beam_merge launch failed");

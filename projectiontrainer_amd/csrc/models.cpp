@@ -960,7 +960,7 @@ int gen_layer(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, int l, G
 
 int gemma_generate(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, const ptk_gemma3_generate_desc* gd,
                    const float* prompt, const int64_t* force, int64_t* out_ids, bf16_t* step_logits, void* ws,
-                   size_t ws_bytes, hipStream_t st) {
+                   size_t ws_bytes, hipStream_t st, float pen = 1.f, int32_t* pen_status = nullptr) {
   const int B = gd->batch, P = gd->prompt_len, NT = gd->max_new_tokens;
   if (B <= 0 || P < 4 || NT <= 0) return set_error("generate: batch %d, prompt_len %d (>= 4), max_new_tokens %d", B, P, NT);
   if (gd->prompt_batch_stride < P) return set_error("generate: prompt_batch_stride %ld < prompt_len %d",
@@ -982,6 +982,11 @@ int gemma_generate(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, con
     CK(gen_gemm(w.dec, w.xf, H, wt->embed, H, w.logits, V, B, V, H, ACT_NONE, st));
     if (step_logits)
       CKH(hipMemcpyAsync(step_logits + (long)t * B * V, w.logits, (size_t)B * V * 2, hipMemcpyDeviceToDevice, st));
+    if (pen != 1.f && t > 0)   // the history: the row's own t tokens so far (the forced ones under teacher forcing)
+      return launch_gen_sample_pen(w.logits, V, B, V, gd->do_sample, gd->top_k, gd->temperature,
+                                   gd->top_p > 0.f ? gd->top_p : 1.f, gd->seed, t, (long)gd->eos_token_id,
+                                   (long)gd->pad_token_id, w.finished, out_ids + t, NT, w.next,
+                                   PenArgs{force ? force : out_ids, NT, t, pen, pen_status}, st);
     return launch_gen_sample(w.logits, V, B, V, gd->do_sample, gd->top_k, gd->temperature,
                              gd->top_p > 0.f ? gd->top_p : 1.f, gd->seed, t,
                              (long)gd->eos_token_id, (long)gd->pad_token_id, w.finished, out_ids + t, NT, w.next, st);
@@ -1232,6 +1237,100 @@ int ptk_gemma3_generate(const ptk_gemma3_config* c, const ptk_gemma3_weights* w,
   if (!c || !w || !g || !prompt_embeds || !out_ids) return set_error("generate: NULL argument");
   return gemma_generate(c, w, g, prompt_embeds, force_ids, out_ids, (bf16_t*)step_logits, ws, ws_bytes,
                         (hipStream_t)stream);
+}
+
+// ---- repetition penalty: additive entry points (the unpenalised ones above keep their signatures) ----
+// the status word of a penalised call sits behind the unpenalised workspace, 16-B aligned
+static int32_t* pen_status_word(void* ws, size_t base_bytes) {
+  return (int32_t*)(((uintptr_t)ws + base_bytes + 15) / 16 * 16);
+}
+
+size_t ptk_sample_next_token_workspace_bytes(int batch) { return (size_t)(batch > 0 ? batch : 0) * 12 + 256; }
+
+int ptk_sample_next_token(const void* logits, int64_t ld, int batch, int vocab, int do_sample, int top_k,
+                          float temperature, float top_p, uint64_t seed, int step, int64_t eos_token_id,
+                          int64_t pad_token_id, int32_t* finished, const int64_t* history, int64_t history_ld,
+                          int n_hist, float repetition_penalty, int64_t* out, void* ws, size_t ws_bytes,
+                          void* stream) {
+  if (!logits || !out || !ws) return set_error("sample_next_token: NULL argument");
+  if (batch <= 0 || vocab <= 0 || ld < vocab) return set_error("sample_next_token: batch %d, vocab %d, ld %ld", batch, vocab, (long)ld);
+  if (ws_bytes < ptk_sample_next_token_workspace_bytes(batch)) return set_error("sample_next_token: workspace too small");
+  PenArgs pa{history, (long)history_ld, n_hist, repetition_penalty, nullptr};
+  if (top_p == 0.f) top_p = 1.f;   // (as ptk_gemma3_generate_desc: 0 reads as 1)
+  // every rule of the step, before the first device call (the launcher runs the same function again)
+  if (gen_sample_validate("sample_next_token", vocab, do_sample, top_k, temperature, top_p, pa)) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  // ws: next int64 [batch] | finished int32 [batch] (when the caller has none) | status, each 16-B aligned
+  int64_t* next = (int64_t*)(((uintptr_t)ws + 15) / 16 * 16);
+  int32_t* fin = (int32_t*)(((uintptr_t)(next + batch) + 15) / 16 * 16);
+  const size_t fin_bytes = ((size_t)batch * 4 + 15) / 16 * 16;
+  pa.status = pen_status_word(fin, fin_bytes);
+  if (!finished) {
+    CK(launch_zero(fin, fin_bytes, st));
+    finished = fin;
+  }
+  if (pen_active(pa)) CK(launch_zero(pa.status, 16, st));
+  CK(launch_gen_sample_pen((const bf16_t*)logits, (long)ld, batch, vocab, do_sample, top_k, temperature, top_p, seed, step, (long)eos_token_id, (long)pad_token_id, finished,
+                           out, 1, next, pa, st));
+  return pen_active(pa) ? pen_status_check("sample_next_token", pa.status, st) : 0;
+}
+
+size_t ptk_beam_candidates_penalized_workspace_bytes(int batch, int beams, int n_cand) {
+  return beam_candidates_ws_bytes(batch, beams, n_cand) + 256;
+}
+
+int ptk_beam_candidates_penalized(const void* logits, int64_t ld, const float* beam_scores, int batch, int beams,
+                                  int vocab, int do_sample, int top_k, float top_p, float temperature,
+                                  int min_tokens_to_keep, uint64_t seed, int step, int n_cand,
+                                  const int64_t* history, int64_t history_ld, int n_hist, float repetition_penalty,
+                                  int64_t* tokens, int32_t* beam_idx, float* scores, void* ws, size_t ws_bytes,
+                                  void* stream) {
+  if (!logits || !beam_scores || !tokens || !beam_idx || !scores) return set_error("beam_candidates: NULL argument");
+  if (ld < vocab) return set_error("beam_candidates: ld < vocab");
+  PenArgs pa{history, (long)history_ld, n_hist, repetition_penalty, nullptr};
+  // every rule of the selection, the workspace size included, before the first device call (the launcher runs the
+  // same function again)
+  if (beam_candidates_validate(batch, beams, vocab, do_sample, top_k, top_p, temperature, min_tokens_to_keep, n_cand,
+                               ws, ws_bytes, pa))
+    return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (pen_active(pa)) {
+    pa.status = pen_status_word(ws, beam_candidates_ws_bytes(batch, beams, n_cand));
+    CK(launch_zero(pa.status, 16, st));
+  }
+  CK(launch_beam_candidates_pen((const bf16_t*)logits, (long)ld, beam_scores, batch, beams, vocab, do_sample, top_k,
+                                top_p, temperature, min_tokens_to_keep, seed, step, n_cand, tokens, beam_idx, scores,
+                                ws, ws_bytes, pa, st));
+  return pen_active(pa) ? pen_status_check("beam_candidates", pa.status, st) : 0;
+}
+
+size_t ptk_gemma3_generate_penalized_workspace_bytes(const ptk_gemma3_config* c, int batch, int prompt_len,
+                                                     int max_new_tokens) {
+  return ptk_gemma3_generate_workspace_bytes(c, batch, prompt_len, max_new_tokens) + 256;
+}
+
+int ptk_gemma3_generate_penalized(const ptk_gemma3_config* c, const ptk_gemma3_weights* w,
+                                  const ptk_gemma3_generate_desc* g, const float* prompt_embeds,
+                                  const int64_t* force_ids, int64_t* out_ids, void* step_logits,
+                                  float repetition_penalty, void* ws, size_t ws_bytes, void* stream) {
+  if (!c || !w || !g || !prompt_embeds || !out_ids) return set_error("generate: NULL argument");
+  // the longest history is max_new_tokens - 1 tokens: the sampling step's rules for it hold for every step, and
+  // are checked here, before the first device call
+  PenArgs pa{out_ids, g->max_new_tokens, g->max_new_tokens > 1 ? g->max_new_tokens - 1 : 0, repetition_penalty, nullptr};
+  if (pen_validate("generate", pa)) return -1;
+  hipStream_t st = (hipStream_t)stream;
+  if (!pen_active(pa))
+    return gemma_generate(c, w, g, prompt_embeds, force_ids, out_ids, (bf16_t*)step_logits, ws, ws_bytes, st);
+  if (gen_sample_validate("generate", c->vocab, g->do_sample, g->top_k, g->temperature,
+                          g->top_p > 0.f ? g->top_p : 1.f, pa))
+    return -1;
+  const size_t base = ptk_gemma3_generate_workspace_bytes(c, g->batch, g->prompt_len, g->max_new_tokens);
+  if (!ws || ws_bytes < base + 256) return set_error("generate: workspace too small");
+  int32_t* status = pen_status_word(ws, base);
+  CK(launch_zero(status, 16, st));
+  CK(gemma_generate(c, w, g, prompt_embeds, force_ids, out_ids, (bf16_t*)step_logits, ws, base, st,
+                    repetition_penalty, status));
+  return pen_status_check("generate", status, st);
 }
 
 int ptk_bf16_sumsq_partial_floats(void) { return scale_sumsq_partial_floats(); }

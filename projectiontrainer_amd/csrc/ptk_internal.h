@@ -462,6 +462,32 @@ int launch_dec_step_prep(int32_t* slot_ok, const int32_t* nvalid, int rows, int 
 int launch_dec_gather_rows(const void* in, void* out, const int32_t* src, int rows, long row_bytes, hipStream_t st);
 int launch_dec_gather_i32(const int32_t* in, int32_t* out, const int32_t* src, int rows, hipStream_t st);
 int launch_dec_repeat_index(int32_t* src, int rows, int repeat, hipStream_t st);
+// repetition penalty (generate.hip): a row's history int64 [rows][ld_hist] (the first n_hist of each), the penalty,
+// and a device word the kernels set when a row's kept list overflowed (zeroed by the caller; pen_status_check
+// copies it back, waits for the stream and turns a set word into an error)
+struct PenArgs {
+  const int64_t* history;
+  long ld_hist;
+  int n_hist;
+  float penalty;
+  int32_t* status;
+};
+inline bool pen_active(const PenArgs& pa) { return pa.n_hist > 0 && pa.penalty != 1.f; }
+int pen_validate(const char* who, const PenArgs& pa);                  // the penalty's arguments alone
+// every host-side rule of a sampling step / a beam selection, penalised or not (no device call); a penalised beam
+// selection needs 256 bytes more workspace than beam_candidates_ws_bytes (its status word)
+int gen_sample_validate(const char* who, int V, int do_sample, int top_k, float temperature, float top_p,
+                        const PenArgs& pa);
+int beam_candidates_validate(int batch, int K, int V, int do_sample, int top_k, float top_p, float temperature,
+                             int min_keep, int n_cand, const void* ws, size_t ws_bytes, const PenArgs& pa);
+int pen_status_check(const char* who, int32_t* status, hipStream_t st);
+int launch_gen_sample_pen(const bf16_t* logits, long ld, int B, int V, int do_sample, int top_k, float temperature,
+                          float top_p, uint64_t seed, int step, long eos_id, long pad_id, int32_t* finished,
+                          int64_t* out, long ld_out, int64_t* next, const PenArgs& pa, hipStream_t st);
+int launch_beam_candidates_pen(const bf16_t* logits, long ld, const float* beam_scores, int batch, int K, int V,
+                               int do_sample, int top_k, float top_p, float temperature, int min_keep, uint64_t seed,
+                               int step, int n_cand, int64_t* tok, int32_t* beam, float* score, void* ws,
+                               size_t ws_bytes, const PenArgs& pa, hipStream_t st);
 size_t beam_candidates_ws_bytes(int batch, int K, int n_cand);
 int launch_beam_candidates(const bf16_t* logits, long ld, const float* beam_scores, int batch, int K, int V,
                            int do_sample, int top_k, float top_p, float temperature, int min_keep, uint64_t seed,

@@ -27,6 +27,23 @@ def _dev(a, dtype, device):
     return t.to(device=device, dtype=dtype).contiguous()
 
 
+QLORA_UNSUPPORTED = ("Gemma3CausalLM.from_hf: quantised / QLoRA (peft) language models are not supported "
+                     "by the HIP Stage-1 path; pass the dense bf16 or fp32 Gemma3ForCausalLM "
+                     "(run without --enable_qlora)")
+
+
+def _check_penalty(p) -> float:
+    """HF's rule for repetition_penalty (RepetitionPenaltyLogitsProcessor): a float > 0; finite here as well.  Any
+    real scalar converts (numpy and 0-d tensor values included); strings and bools do not count as numbers."""
+    try:
+        v = float("nan") if isinstance(p, (bool, str, bytes)) else float(p)
+    except (TypeError, ValueError):
+        v = float("nan")
+    if not (0.0 < v < float("inf")):
+        raise L.PtkError(f"repetition_penalty must be a finite float > 0, got {p!r}")
+    return v
+
+
 def interleave_gate_up(gate, up):
     """[I,H],[I,H] -> [2I,H]: rows 32q..32q+15 = gate[16q..16q+15], 32q+16.. = up[16q..]."""
     I, H = gate.shape
@@ -141,9 +158,7 @@ class Gemma3CausalLM:
         qc = getattr(getattr(model, "config", None), "quantization_config", None)
         if (getattr(model, "is_loaded_in_4bit", False) or getattr(model, "is_loaded_in_8bit", False)
                 or getattr(model, "is_quantized", False) or qc is not None or hasattr(model, "peft_config")):
-            raise ValueError("Gemma3CausalLM.from_hf: quantised / QLoRA (peft) language models are not supported "
-                             "by the HIP Stage-1 path; pass the dense bf16 or fp32 Gemma3ForCausalLM "
-                             "(run without --enable_qlora)")
+            raise ValueError(QLORA_UNSUPPORTED)
 
     @classmethod
     def from_hf(cls, model, device="cuda", max_pos=2048, frozen=True):
@@ -157,6 +172,8 @@ class Gemma3CausalLM:
         if gc is not None:
             lm.generation_defaults = {k: getattr(gc, k) for k in ("top_k", "top_p", "temperature")
                                       if getattr(gc, k, None) is not None}
+            if getattr(gc, "repetition_penalty", None) not in (None, 1.0):   # (1.0: HF's "no penalty")
+                lm.generation_defaults["repetition_penalty"] = float(gc.repetition_penalty)
         return lm
 
     @classmethod
@@ -234,7 +251,7 @@ class Gemma3CausalLM:
 
     def generate(self, inputs_embeds, max_new_tokens=64, do_sample=True, top_k=None, temperature=None,
                  pad_token_id=None, eos_token_id=None, seed=0, prompt_len=None, batch=None, force_ids=None,
-                 return_logits=False, top_p=None):
+                 return_logits=False, top_p=None, repetition_penalty=None):
         """`Gemma3ForCausalLM.generate(inputs_embeds=, attention_mask=ones, max_new_tokens=, do_sample=, pad_token_id=,
         eos_token_id=)` as the reference's validation calls it (Stage1/projector_trainer.py:386-393) on the KV-cache
         decode of libptk (ptk_gemma3_generate): returns the NEW tokens, int64 [B, n], n = max_new_tokens or the step
@@ -245,7 +262,10 @@ class Gemma3CausalLM:
         (torch.multinomial's stream is not reproduced).
         inputs_embeds: f32 [B, P, H], or [B * stride, H] rows with prompt_len = P and batch = B (the Stage-1
         engine's LLM input, whose vision rows start each stride-row sample).  force_ids (int64 [B, max_new_tokens]): teacher forcing
-        (step t feeds force_ids[:, t-1]); return_logits: also the bf16 logits of every step [max_new_tokens, B, V]."""
+        (step t feeds force_ids[:, t-1]); return_logits: also the bf16 logits of every step [max_new_tokens, B, V].
+        repetition_penalty (None: generation_defaults, else 1.0): HF's RepetitionPenaltyLogitsProcessor over the
+        row's own new tokens (the forced ones under teacher forcing), on the fp32 raw logits before the warpers;
+        1.0 is the unpenalised call (ptk_gemma3_generate)."""
         if inputs_embeds.dtype != torch.float32 or not inputs_embeds.is_cuda or not inputs_embeds.is_contiguous():
             raise L.PtkError("generate: inputs_embeds must be a contiguous f32 HIP tensor")
         H = self.cfg.hidden_size
@@ -265,9 +285,12 @@ class Gemma3CausalLM:
         top_k = dflt.get("top_k", 50) if top_k is None else top_k
         top_p = dflt.get("top_p", 1.0) if top_p is None else top_p
         temperature = dflt.get("temperature", 1.0) if temperature is None else temperature
+        penalty = _check_penalty(dflt.get("repetition_penalty", 1.0) if repetition_penalty is None
+                                 else repetition_penalty)
         desc = L.Gemma3GenerateC(B, P, max_new_tokens, int(bool(do_sample)), int(top_k or 0), float(temperature),
                                  int(seed) & ((1 << 64) - 1), eos, pad, stride, float(top_p))
-        n = L.lib().ptk_gemma3_generate_workspace_bytes(self.c_cfg, B, P, max_new_tokens)
+        ws_fn = "ptk_gemma3_generate" + ("" if penalty == 1.0 else "_penalized") + "_workspace_bytes"
+        n = getattr(L.lib(), ws_fn)(self.c_cfg, B, P, max_new_tokens)
         if getattr(self, "_gen_ws", None) is None or self._gen_ws.numel() < n:
             self._gen_ws = None
             self._gen_ws = torch.empty(n, dtype=torch.uint8, device=self.device)
@@ -278,10 +301,13 @@ class Gemma3CausalLM:
             force_ids = force_ids.to(device=self.device, dtype=torch.int64).contiguous()
             if tuple(force_ids.shape) != (B, max_new_tokens):
                 raise L.PtkError(f"generate: force_ids must be [{B}, {max_new_tokens}]")
-        L.check(L.lib().ptk_gemma3_generate(self.c_cfg, self.c_w, desc, inputs_embeds.data_ptr(),
-                                            0 if force_ids is None else force_ids.data_ptr(), out.data_ptr(),
-                                            0 if logits is None else logits.data_ptr(), self._gen_ws.data_ptr(),
-                                            self._gen_ws.numel(), L.stream_ptr(self.device)), "ptk_gemma3_generate")
+        args = (self.c_cfg, self.c_w, desc, inputs_embeds.data_ptr(), 0 if force_ids is None else force_ids.data_ptr(),
+                out.data_ptr(), 0 if logits is None else logits.data_ptr())
+        tail = (self._gen_ws.data_ptr(), self._gen_ws.numel(), L.stream_ptr(self.device))
+        if penalty == 1.0:
+            L.check(L.lib().ptk_gemma3_generate(*args, *tail), "ptk_gemma3_generate")
+        else:
+            L.check(L.lib().ptk_gemma3_generate_penalized(*args, penalty, *tail), "ptk_gemma3_generate_penalized")
         n_out = max_new_tokens
         if eos >= 0:   # HF stops after the step at which the last unfinished row produced EOS
             done = (out == eos).cumsum(1) > 0
@@ -336,17 +362,34 @@ class Gemma3CausalLM:
         return logits
 
     def beam_candidates(self, logits, beam_scores, beams, n_cand, do_sample, top_k, top_p, temperature, seed, step,
-                        min_tokens_to_keep):
-        """ptk_beam_candidates over logits [B * beams, V]: (tokens int64, beam int32, accumulated f32) [B, n_cand]."""
+                        min_tokens_to_keep, history=None, repetition_penalty=1.0):
+        """ptk_beam_candidates over logits [B * beams, V]: (tokens int64, beam int32, accumulated f32) [B, n_cand].
+        history (int64 [B * beams, t], each row's running hypothesis) with repetition_penalty != 1: the log probs
+        of its distinct tokens are penalised before the warpers (ptk_beam_candidates_penalized)."""
         rows, V = logits.shape
         B = rows // beams
         tok = torch.empty((B, n_cand), dtype=torch.int64, device=self.device)
         bi = torch.empty((B, n_cand), dtype=torch.int32, device=self.device)
         sc = torch.empty((B, n_cand), dtype=torch.float32, device=self.device)
         bs = beam_scores.to(device=self.device, dtype=torch.float32).contiguous()
-        n = L.lib().ptk_beam_candidates_workspace_bytes(B, beams, n_cand)
+        penalty = _check_penalty(repetition_penalty)
+        n_hist = 0 if history is None else int(history.shape[-1])
+        penalised = penalty != 1.0 and n_hist > 0
+        ws_fn = "ptk_beam_candidates_penalized_workspace_bytes" if penalised else "ptk_beam_candidates_workspace_bytes"
+        n = getattr(L.lib(), ws_fn)(B, beams, n_cand)
         if getattr(self, "_bc_ws", None) is None or self._bc_ws.numel() < n:
             self._bc_ws = torch.empty(n, dtype=torch.uint8, device=self.device)
+        if penalised:
+            hist = history.to(device=self.device, dtype=torch.int64)
+            if hist.dim() != 2 or hist.shape[0] != rows or hist.stride(1) != 1:   # (rows of a wider buffer pass as is)
+                hist = hist.reshape(rows, n_hist).contiguous()
+            L.check(L.lib().ptk_beam_candidates_penalized(
+                logits.data_ptr(), V, bs.data_ptr(), B, beams, V, int(bool(do_sample)), int(top_k or 0), float(top_p),
+                float(temperature), int(min_tokens_to_keep), int(seed) & ((1 << 64) - 1), int(step), int(n_cand),
+                hist.data_ptr(), hist.stride(0), n_hist, penalty, tok.data_ptr(), bi.data_ptr(), sc.data_ptr(),
+                self._bc_ws.data_ptr(), self._bc_ws.numel(), L.stream_ptr(self.device)),
+                "ptk_beam_candidates_penalized")
+            return tok, bi, sc
         L.check(L.lib().ptk_beam_candidates(logits.data_ptr(), V, bs.data_ptr(), B, beams, V, int(bool(do_sample)),
                                             int(top_k or 0), float(top_p), float(temperature), int(min_tokens_to_keep),
                                             int(seed) & ((1 << 64) - 1), int(step), int(n_cand), tok.data_ptr(),
@@ -356,12 +399,14 @@ class Gemma3CausalLM:
 
     def beam_generate(self, inputs_embeds, attention_mask=None, num_beams=3, max_new_tokens=512, do_sample=True,
                       top_k=50, top_p=1.0, temperature=1.0, eos_token_id=None, pad_token_id=None,
-                      length_penalty=1.0, early_stopping=False, seed=0):
+                      length_penalty=1.0, early_stopping=False, seed=0, repetition_penalty=1.0):
         """`generate(inputs_embeds=, attention_mask=, num_beams=, do_sample=, top_k=, top_p=, ...)` with beams, as
         Stage 2's validation calls it (Stage2/trainer.py:596-626 -> GenerationMixin._beam_search): the stepwise
         KV-cache decode, ptk_beam_candidates for the continuations of each step (sampled without replacement from
         the joint beam x vocab distribution, or the best with do_sample=False) and the host bookkeeping of
-        projectiontrainer_amd/beam.py.  Returns the new tokens of the best hypothesis per prompt, int64 [B, n]."""
+        projectiontrainer_amd/beam.py.  repetition_penalty: each row's running hypothesis (after the beam
+        re-order) penalises the log probs of its tokens, as HF's processor does inside _beam_search.  Returns the
+        new tokens of the best hypothesis per prompt, int64 [B, n]."""
         from .beam import BeamSearch
         B = inputs_embeds.shape[0]
         K = int(num_beams)
@@ -369,15 +414,26 @@ class Gemma3CausalLM:
         n_cand = max(2, 1 + n_eos) * K
         min_keep = (1 + n_eos) if K > 1 else 1
         pad = self.cfg.pad_token_id if pad_token_id is None else int(pad_token_id)
+        penalty = _check_penalty(repetition_penalty)
         bs = BeamSearch(B, K, max_new_tokens, eos_token_id, pad, length_penalty, early_stopping)
         logits = self.decode_begin(inputs_embeds, attention_mask, repeat=K, max_new_tokens=max_new_tokens)
+        # the rows' running hypotheses (BeamSearch.run_seq[:, :, :step]) kept on the device for the penalty: each step
+        # re-orders them by the source rows and appends the tokens that decode_next takes anyway, so no step uploads
+        # its whole history
+        run = (torch.zeros((B * K, max_new_tokens), dtype=torch.int64, device=self.device)
+               if penalty != 1.0 else None)
         step = 0
         while True:
+            hist = run[:, :step] if run is not None and step > 0 else None
             tok, bi, sc = self.beam_candidates(logits, bs.run_score.reshape(-1), K, n_cand, do_sample, top_k, top_p,
-                                               temperature, seed, step, min_keep)
+                                               temperature, seed, step, min_keep, hist, penalty)
             ids, rows = bs.step(tok, bi, sc)
             if bs.finished:
                 break
             step += 1
+            ids, rows = ids.to(self.device), rows.to(self.device)
+            if run is not None:
+                run = run[rows.long()]
+                run[:, step - 1] = ids
             logits = self.decode_next(step, ids, rows)
         return bs.result().to(self.device)

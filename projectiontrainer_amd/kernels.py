@@ -273,3 +273,28 @@ def flash_attn_bwd(Q, K, V, O, dO, lse, *, rows, nkeys, head_dim, batch, batch_i
             d.workspace, d.workspace_bytes = ptr(ws), nb
     check(L.lib().ptk_flash_attn_bwd(d, L.stream_ptr(Q.device)), "flash_attn_bwd")
     return dQ, dK, dV
+
+
+def sample_next_token(logits, *, do_sample=False, top_k=0, temperature=1.0, top_p=1.0, seed=0, step=0,
+                      eos_token_id=-1, pad_token_id=0, finished=None, history=None, repetition_penalty=1.0):
+    """One sampling step of the decode over bf16 logits [B, V] (ptk_sample_next_token): int64 [B].  history
+    (int64 [B, n]): each row's tokens so far, for repetition_penalty; finished (int32 [B], updated) or None."""
+    _require_cuda(logits, finished, history)
+    if logits.dim() != 2 or logits.dtype != torch.bfloat16 or logits.stride(1) != 1:
+        raise L.PtkError("sample_next_token: logits must be bf16 [B, V] with contiguous rows")
+    if finished is not None and (finished.dtype != torch.int32 or not finished.is_contiguous()):
+        raise L.PtkError("sample_next_token: finished must be contiguous int32 [B]")
+    B, V = logits.shape
+    out = torch.empty(B, dtype=torch.int64, device=logits.device)
+    n = L.lib().ptk_sample_next_token_workspace_bytes(B)
+    ws = torch.empty(n, dtype=torch.uint8, device=logits.device)
+    n_hist = 0 if history is None else int(history.shape[1])
+    if history is not None and (history.dtype != torch.int64 or history.stride(1) != 1):
+        raise L.PtkError("sample_next_token: history must be int64 with contiguous rows")
+    check(L.lib().ptk_sample_next_token(ptr(logits), logits.stride(0), B, V, int(bool(do_sample)), int(top_k or 0),
+                                        float(temperature), float(top_p), int(seed) & ((1 << 64) - 1), int(step),
+                                        int(eos_token_id), int(pad_token_id), ptr(finished), ptr(history),
+                                        history.stride(0) if history is not None else 0, n_hist,
+                                        float(repetition_penalty), ptr(out), ptr(ws), n, L.stream_ptr(logits.device)),
+          "ptk_sample_next_token")
+    return out
