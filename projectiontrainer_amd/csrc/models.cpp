@@ -9,9 +9,9 @@
 // be captured into a hipGraph.  Layouts (row-major, token rows b*S + s):
 //   LLM hidden x: f32 [B*Spad, H] (fp32 residual stream, as the reference's
 //   autocast keeps it); GEMM operands bf16.  Attention per (b, kv-head) z:
-//   Q [B,Hkv,S,G,D] (rows (s,j) contiguous), K/V [B,Hkv,S,D], scores/P
-//   [B*Hkv, S*G, S].  QK^T and P.V run on the MFMA GEMM; masks/softmax are
-//   row kernels.
+//   Q [B,Hkv,S,G,D] (rows (s,j) contiguous), K/V [B,Hkv,S,D]; the flash
+//   kernels (flash.hip) keep scores and probabilities on chip, with the masks
+//   and the softmax inside them.
 #include <cstdlib>
 #include <algorithm>
 #include <math.h>
@@ -88,12 +88,14 @@ static int residual_norm_bwd_grads(const float* x2, const float* w_pre, const fl
   if (g_pre) CK(launch_rms_wgrad_bx(t, H, ident, rstd_t, dR, H, 1, M, H, g_post, wpart, st));
   return 0;
 }
+// a runtime switch of the product library: on iff the variable starts with '1' (each caller reads it once)
+static bool env_flag(const char* name) {
+  const char* e = getenv(name);
+  return e && e[0] == '1';
+}
 // PTK_DKV_REDUCE_SPLIT=1: separate attn_dkv_reduce_kernel pass (A/B) instead of summing the split-slab
 // dK/dV partials inside qknorm_rope_bwd
-static bool dkv_reduce_split() {
-  static const int v = [] { const char* e = getenv("PTK_DKV_REDUCE_SPLIT"); return e && e[0] == '1' ? 1 : 0; }();
-  return v != 0;
-}
+static bool dkv_reduce_split() { static const bool v = env_flag("PTK_DKV_REDUCE_SPLIT"); return v; }
 
 // PTK_CE_TWO_PASS=1: the cross-entropy pass computes its own row statistics (two reads of the logits) instead
 // of taking them from the lm_head GEMM's epilogue (A/B; tests/test_stage1_gpu.py checks both agree)
@@ -102,17 +104,14 @@ static bool dkv_reduce_split() {
 // CE, timed against the shipped chain.  The product library has no such switch.
 static bool lm_stats_only() {
 #ifdef PTK_DIAG
-  static const int v = [] { const char* e = getenv("PTK_LM_STATS_ONLY"); return e && e[0] == '1' ? 1 : 0; }();
-  return v != 0;
+  static const bool v = env_flag("PTK_LM_STATS_ONLY");
+  return v;
 #else
   return false;
 #endif
 }
 
-static bool ce_two_pass() {
-  static const int v = [] { const char* e = getenv("PTK_CE_TWO_PASS"); return e && e[0] == '1' ? 1 : 0; }();
-  return v != 0;
-}
+static bool ce_two_pass() { static const bool v = env_flag("PTK_CE_TWO_PASS"); return v; }
 
 // PTK_A_KTILED (result-preserving, read once; ptk_a_ktiled_reload re-reads it for tests): 0 = the Gemma MLP
 // activations h and dg | du stay row-major; 2 = they go k-step-tiled between their producer and consumer GEMMs
@@ -180,9 +179,9 @@ struct GemmaLayerSave {
 struct GemmaWs {
   std::vector<float*> x;          // L+1 residual-stream snapshots
   std::vector<GemmaLayerSave> L;
-  bf16_t *P, *xn, *O, *h, *Vt, *Kt, *Qt, *dqkv, *dgu, *dao, *dO, *dS, *dST, *PT, *dOT, *dQ, *dK, *dV, *xf, *logits;
+  bf16_t *xn, *h, *dqkv, *dgu, *dao, *dO, *dQ, *dK, *dV, *xf, *logits;
   bf16_t* dtmp;             // bf16 dX of the q|k|v / gate|up projections (see the workspace layout)
-  float *S, *rstd_f, *row_loss, *dxf, *dxf_part, *count, *gscale, *delta;
+  float *rstd_f, *row_loss, *dxf, *dxf_part, *count, *gscale, *delta;
   float* ce_stats = nullptr;   // the lm_head epilogue's softmax statistics [R][V / 64] (float2)
   float* dkv_part;          // split-query dK/dV partials of the attention backward
   size_t dkv_part_bytes;
@@ -230,14 +229,8 @@ GemmaWs gemma_layout(Bump& bp, const ptk_gemma3_config* c, int B, int T, int Sp,
     }
     w.L.push_back(s);
   }
-  w.P = nullptr;
   w.xn = bp.take<bf16_t>(M * H);
-  w.O = nullptr;
   w.h = bp.take<bf16_t>(M * I);
-  w.Vt = nullptr;
-  w.Kt = nullptr;
-  w.Qt = nullptr;
-  w.S = nullptr;
   w.delta = bp.take<float>(Z * SG);
   {
     FlashBwdArgs fa;
@@ -256,10 +249,6 @@ GemmaWs gemma_layout(Bump& bp, const ptk_gemma3_config* c, int B, int T, int Sp,
   w.dtmp = bp.take<bf16_t>(M * H);
   w.dao = bp.take<bf16_t>(M * H);
   w.dO = bp.take<bf16_t>(Z * SG * D);
-  w.dS = nullptr;
-  w.dST = nullptr;
-  w.PT = nullptr;
-  w.dOT = nullptr;
   w.dQ = bp.take<bf16_t>(Z * SG * D);
   w.dK = bp.take<bf16_t>(Z * Sp * D);
   w.dV = bp.take<bf16_t>(Z * Sp * D);
@@ -958,6 +947,23 @@ int gen_layer(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, int l, G
   return 0;
 }
 
+// the layer stack over pass g, whose g.xa holds the embedded rows: the first layer's input norm, then every layer
+// (gen_layer's arguments), the residual stream alternating between g.xa and g.xb.  Returns the final residual
+// (nullptr: a launch failed).
+const float* gen_stack(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, GenPass& g, int B, int S, int Sp,
+                       int p0, bool prefill, int Smax, const std::vector<bf16_t*>& kc, const std::vector<bf16_t*>& vc,
+                       hipStream_t st, const DecMasks* dm = nullptr) {
+  const int H = c->hidden;
+  if (launch_rmsnorm_fwd(g.xa, H, RowMap{0, 0, 0, 0}, wt->layers[0].ln_in, g.xn, g.rs1, B * Sp, H, c->eps, st))
+    return nullptr;
+  float *xi = g.xa, *xo = g.xb;
+  for (int l = 0; l < c->layers; ++l) {
+    if (gen_layer(c, wt, l, g, xi, xo, B, S, Sp, p0, prefill, Smax, kc[l], vc[l], st, dm)) return nullptr;
+    std::swap(xi, xo);
+  }
+  return xi;
+}
+
 int gemma_generate(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, const ptk_gemma3_generate_desc* gd,
                    const float* prompt, const int64_t* force, int64_t* out_ids, bf16_t* step_logits, void* ws,
                    size_t ws_bytes, hipStream_t st, float pen = 1.f, int32_t* pen_status = nullptr) {
@@ -982,26 +988,19 @@ int gemma_generate(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, con
     CK(gen_gemm(w.dec, w.xf, H, wt->embed, H, w.logits, V, B, V, H, ACT_NONE, st));
     if (step_logits)
       CKH(hipMemcpyAsync(step_logits + (long)t * B * V, w.logits, (size_t)B * V * 2, hipMemcpyDeviceToDevice, st));
-    if (pen != 1.f && t > 0)   // the history: the row's own t tokens so far (the forced ones under teacher forcing)
-      return launch_gen_sample_pen(w.logits, V, B, V, gd->do_sample, gd->top_k, gd->temperature,
-                                   gd->top_p > 0.f ? gd->top_p : 1.f, gd->seed, t, (long)gd->eos_token_id,
-                                   (long)gd->pad_token_id, w.finished, out_ids + t, NT, w.next,
-                                   PenArgs{force ? force : out_ids, NT, t, pen, pen_status}, st);
+    // the history: the row's own t tokens so far (the forced ones under teacher forcing)
     return launch_gen_sample(w.logits, V, B, V, gd->do_sample, gd->top_k, gd->temperature,
-                             gd->top_p > 0.f ? gd->top_p : 1.f, gd->seed, t,
-                             (long)gd->eos_token_id, (long)gd->pad_token_id, w.finished, out_ids + t, NT, w.next, st);
+                             gd->top_p > 0.f ? gd->top_p : 1.f, gd->seed, t, (long)gd->eos_token_id,
+                             (long)gd->pad_token_id, w.finished, out_ids + t, NT, w.next,
+                             PenArgs{force ? force : out_ids, NT, t, pen, pen_status}, st);
   };
   // prefill: the prompt rows, padded per sample to Pp (masked keys), every layer's K / V into the cache
   {
     GenPass& g = w.pre;
     CK(launch_gen_prompt(prompt, (long)gd->prompt_batch_stride, B, P, Pp, H, g.xa, g.kv, st));
-    CK(launch_rmsnorm_fwd(g.xa, H, RowMap{0, 0, 0, 0}, wt->layers[0].ln_in, g.xn, g.rs1, B * Pp, H, c->eps, st));
-    float *xi = g.xa, *xo = g.xb;
-    for (int l = 0; l < c->layers; ++l) {
-      CK(gen_layer(c, wt, l, g, xi, xo, B, P, Pp, 0, true, Smax, w.kc[l], w.vc[l], st));
-      std::swap(xi, xo);
-    }
-    CK(head(xi, RowMap{1, 0, Pp, P - 1}, 0));   // the last prompt position of each sample
+    const float* x = gen_stack(c, wt, g, B, P, Pp, 0, true, Smax, w.kc, w.vc, st);
+    if (!x) return -1;
+    CK(head(x, RowMap{1, 0, Pp, P - 1}, 0));   // the last prompt position of each sample
   }
   // decode: step t feeds the token drawn at t - 1 (or force[:, t - 1]) at position P + t - 1
   for (int t = 1; t < NT; ++t) {
@@ -1013,13 +1012,9 @@ int gemma_generate(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, con
       ids = w.feed;
     }
     CK(launch_build_llm_inputs((const bf16_t*)wt->embed, ids, B, 1, 0, 1, 1, H, escale, -1, g.xa, g.kv, st));
-    CK(launch_rmsnorm_fwd(g.xa, H, RowMap{0, 0, 0, 0}, wt->layers[0].ln_in, g.xn, g.rs1, B, H, c->eps, st));
-    float *xi = g.xa, *xo = g.xb;
-    for (int l = 0; l < c->layers; ++l) {
-      CK(gen_layer(c, wt, l, g, xi, xo, B, 1, 1, p, false, Smax, w.kc[l], w.vc[l], st));
-      std::swap(xi, xo);
-    }
-    CK(head(xi, RowMap{0, 0, 0, 0}, t));
+    const float* x = gen_stack(c, wt, g, B, 1, 1, p, false, Smax, w.kc, w.vc, st);
+    if (!x) return -1;
+    CK(head(x, RowMap{0, 0, 0, 0}, t));
   }
   return 0;
 }
@@ -1113,14 +1108,10 @@ int gemma_decode_prefill(const ptk_gemma3_config* c, const ptk_gemma3_weights* w
   GenPass& g = w.pre;
   CK(launch_dec_prompt(prompt, (long)d->prompt_batch_stride, mask, mask_ld, 1, Bp, P, Pp, H, g.xa, g.kv, st));
   CK(launch_dec_positions(g.kv, Bp, P, Pp, Smax, w.pos_pre, w.slot_ok, w.nvalid, st));
-  CK(launch_rmsnorm_fwd(g.xa, H, RowMap{0, 0, 0, 0}, wt->layers[0].ln_in, g.xn, g.rs1, Bp * Pp, H, c->eps, st));
   DecMasks dm{};
   dm.pos = w.pos_pre;
-  float *xi = g.xa, *xo = g.xb;
-  for (int l = 0; l < c->layers; ++l) {
-    CK(gen_layer(c, wt, l, g, xi, xo, Bp, P, Pp, 0, true, Smax, w.kc[l], w.vc[l], st, &dm));
-    std::swap(xi, xo);
-  }
+  const float* xi = gen_stack(c, wt, g, Bp, P, Pp, 0, true, Smax, w.kc, w.vc, st, &dm);
+  if (!xi) return -1;
   CK(launch_rmsnorm_fwd(xi, H, RowMap{1, 0, Pp, P - 1}, wt->final_norm, w.xf, w.rstd_f, Bp, H, c->eps, st));
   bf16_t* lg = R == 1 ? logits : w.logits_pre;
   CK(launch_gemm(gemm(w.xf, H, wt->embed, H, lg, V, Bp, V, H), ACT_NONE, OUT_BF16, 1, st));
@@ -1156,12 +1147,8 @@ int gemma_decode_step(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, 
   GenPass& g = w.dec;
   const float escale = bfround_host(sqrtf((float)H));
   CK(launch_build_llm_inputs((const bf16_t*)wt->embed, ids, rows, 1, 0, 1, 1, H, escale, -1, g.xa, g.kv, st));
-  CK(launch_rmsnorm_fwd(g.xa, H, RowMap{0, 0, 0, 0}, wt->layers[0].ln_in, g.xn, g.rs1, rows, H, c->eps, st));
-  float *xi = g.xa, *xo = g.xb;
-  for (int l = 0; l < c->layers; ++l) {
-    CK(gen_layer(c, wt, l, g, xi, xo, rows, 1, 1, p0, false, w.Smax, w.kc[l], w.vc[l], st, &dm));
-    std::swap(xi, xo);
-  }
+  const float* xi = gen_stack(c, wt, g, rows, 1, 1, p0, false, w.Smax, w.kc, w.vc, st, &dm);
+  if (!xi) return -1;
   CK(launch_rmsnorm_fwd(xi, H, RowMap{0, 0, 0, 0}, wt->final_norm, w.xf, w.rstd_f, rows, H, c->eps, st));
   CK(gen_gemm(w.dec, w.xf, H, wt->embed, H, logits, V, rows, V, H, ACT_NONE, st));
   return 0;
@@ -1198,17 +1185,6 @@ size_t ptk_beam_candidates_workspace_bytes(int batch, int beams, int n_cand) {
   return beam_candidates_ws_bytes(batch, beams, n_cand);
 }
 
-int ptk_beam_candidates(const void* logits, int64_t ld, const float* beam_scores, int batch, int beams, int vocab,
-                        int do_sample, int top_k, float top_p, float temperature, int min_tokens_to_keep,
-                        uint64_t seed, int step, int n_cand, int64_t* tokens, int32_t* beam_idx, float* scores,
-                        void* ws, size_t ws_bytes, void* stream) {
-  if (!logits || !beam_scores || !tokens || !beam_idx || !scores) return set_error("beam_candidates: NULL argument");
-  if (ld < vocab) return set_error("beam_candidates: ld < vocab");
-  return launch_beam_candidates((const bf16_t*)logits, (long)ld, beam_scores, batch, beams, vocab, do_sample, top_k,
-                                top_p, temperature, min_tokens_to_keep, seed, step, n_cand, tokens, beam_idx, scores,
-                                ws, ws_bytes, (hipStream_t)stream);
-}
-
 int ptk_gemma3_loss_fwd_bwd(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, const ptk_gemma3_batch* bt,
                             void* ws, size_t ws_bytes, void* stream) {
   return gemma_run(c, wt, bt, nullptr, ws, ws_bytes, (hipStream_t)stream);
@@ -1231,15 +1207,7 @@ size_t ptk_gemma3_generate_workspace_bytes(const ptk_gemma3_config* c, int batch
   return bp.off + 256;
 }
 
-int ptk_gemma3_generate(const ptk_gemma3_config* c, const ptk_gemma3_weights* w, const ptk_gemma3_generate_desc* g,
-                        const float* prompt_embeds, const int64_t* force_ids, int64_t* out_ids, void* step_logits,
-                        void* ws, size_t ws_bytes, void* stream) {
-  if (!c || !w || !g || !prompt_embeds || !out_ids) return set_error("generate: NULL argument");
-  return gemma_generate(c, w, g, prompt_embeds, force_ids, out_ids, (bf16_t*)step_logits, ws, ws_bytes,
-                        (hipStream_t)stream);
-}
-
-// ---- repetition penalty: additive entry points (the unpenalised ones above keep their signatures) ----
+// ---- token selection and generate: the entry points with a repetition penalty, and the plain ones through them ----
 // the status word of a penalised call sits behind the unpenalised workspace, 16-B aligned
 static int32_t* pen_status_word(void* ws, size_t base_bytes) {
   return (int32_t*)(((uintptr_t)ws + base_bytes + 15) / 16 * 16);
@@ -1270,8 +1238,8 @@ int ptk_sample_next_token(const void* logits, int64_t ld, int batch, int vocab, 
     finished = fin;
   }
   if (pen_active(pa)) CK(launch_zero(pa.status, 16, st));
-  CK(launch_gen_sample_pen((const bf16_t*)logits, (long)ld, batch, vocab, do_sample, top_k, temperature, top_p, seed, step, (long)eos_token_id, (long)pad_token_id, finished,
-                           out, 1, next, pa, st));
+  CK(launch_gen_sample((const bf16_t*)logits, (long)ld, batch, vocab, do_sample, top_k, temperature, top_p, seed, step,
+                       (long)eos_token_id, (long)pad_token_id, finished, out, 1, next, pa, st));
   return pen_active(pa) ? pen_status_check("sample_next_token", pa.status, st) : 0;
 }
 
@@ -1279,6 +1247,8 @@ size_t ptk_beam_candidates_penalized_workspace_bytes(int batch, int beams, int n
   return beam_candidates_ws_bytes(batch, beams, n_cand) + 256;
 }
 
+// every rule of the selection, the workspace size included, before the first device call (the launcher runs the same
+// function again)
 int ptk_beam_candidates_penalized(const void* logits, int64_t ld, const float* beam_scores, int batch, int beams,
                                   int vocab, int do_sample, int top_k, float top_p, float temperature,
                                   int min_tokens_to_keep, uint64_t seed, int step, int n_cand,
@@ -1288,8 +1258,6 @@ int ptk_beam_candidates_penalized(const void* logits, int64_t ld, const float* b
   if (!logits || !beam_scores || !tokens || !beam_idx || !scores) return set_error("beam_candidates: NULL argument");
   if (ld < vocab) return set_error("beam_candidates: ld < vocab");
   PenArgs pa{history, (long)history_ld, n_hist, repetition_penalty, nullptr};
-  // every rule of the selection, the workspace size included, before the first device call (the launcher runs the
-  // same function again)
   if (beam_candidates_validate(batch, beams, vocab, do_sample, top_k, top_p, temperature, min_tokens_to_keep, n_cand,
                                ws, ws_bytes, pa))
     return -1;
@@ -1298,10 +1266,21 @@ int ptk_beam_candidates_penalized(const void* logits, int64_t ld, const float* b
     pa.status = pen_status_word(ws, beam_candidates_ws_bytes(batch, beams, n_cand));
     CK(launch_zero(pa.status, 16, st));
   }
-  CK(launch_beam_candidates_pen((const bf16_t*)logits, (long)ld, beam_scores, batch, beams, vocab, do_sample, top_k,
-                                top_p, temperature, min_tokens_to_keep, seed, step, n_cand, tokens, beam_idx, scores,
-                                ws, ws_bytes, pa, st));
+  CK(launch_beam_candidates((const bf16_t*)logits, (long)ld, beam_scores, batch, beams, vocab, do_sample, top_k, top_p,
+                            temperature, min_tokens_to_keep, seed, step, n_cand, tokens, beam_idx, scores, ws, ws_bytes,
+                            pa, st));
   return pen_active(pa) ? pen_status_check("beam_candidates", pa.status, st) : 0;
+}
+
+// the unpenalised selection is the penalised one with no history (kNoPen): the same checks, workspace and kernels
+int ptk_beam_candidates(const void* logits, int64_t ld, const float* beam_scores, int batch, int beams, int vocab,
+                        int do_sample, int top_k, float top_p, float temperature, int min_tokens_to_keep,
+                        uint64_t seed, int step, int n_cand, int64_t* tokens, int32_t* beam_idx, float* scores,
+                        void* ws, size_t ws_bytes, void* stream) {
+  return ptk_beam_candidates_penalized(logits, ld, beam_scores, batch, beams, vocab, do_sample, top_k, top_p,
+                                       temperature, min_tokens_to_keep, seed, step, n_cand, kNoPen.history,
+                                       kNoPen.ld_hist, kNoPen.n_hist, kNoPen.penalty, tokens, beam_idx, scores, ws,
+                                       ws_bytes, stream);
 }
 
 size_t ptk_gemma3_generate_penalized_workspace_bytes(const ptk_gemma3_config* c, int batch, int prompt_len,
@@ -1309,16 +1288,16 @@ size_t ptk_gemma3_generate_penalized_workspace_bytes(const ptk_gemma3_config* c,
   return ptk_gemma3_generate_workspace_bytes(c, batch, prompt_len, max_new_tokens) + 256;
 }
 
-int ptk_gemma3_generate_penalized(const ptk_gemma3_config* c, const ptk_gemma3_weights* w,
-                                  const ptk_gemma3_generate_desc* g, const float* prompt_embeds,
-                                  const int64_t* force_ids, int64_t* out_ids, void* step_logits,
-                                  float repetition_penalty, void* ws, size_t ws_bytes, void* stream) {
+// ptk_gemma3_generate (penalty == nullptr: it has no penalty argument to check) and ptk_gemma3_generate_penalized
+static int generate_entry(const ptk_gemma3_config* c, const ptk_gemma3_weights* w, const ptk_gemma3_generate_desc* g,
+                          const float* prompt_embeds, const int64_t* force_ids, int64_t* out_ids, void* step_logits,
+                          const float* penalty, void* ws, size_t ws_bytes, hipStream_t st) {
   if (!c || !w || !g || !prompt_embeds || !out_ids) return set_error("generate: NULL argument");
   // the longest history is max_new_tokens - 1 tokens: the sampling step's rules for it hold for every step, and
   // are checked here, before the first device call
-  PenArgs pa{out_ids, g->max_new_tokens, g->max_new_tokens > 1 ? g->max_new_tokens - 1 : 0, repetition_penalty, nullptr};
-  if (pen_validate("generate", pa)) return -1;
-  hipStream_t st = (hipStream_t)stream;
+  PenArgs pa{out_ids, g->max_new_tokens, g->max_new_tokens > 1 ? g->max_new_tokens - 1 : 0, penalty ? *penalty : 1.f,
+             nullptr};
+  if (penalty && pen_validate("generate", pa)) return -1;
   if (!pen_active(pa))
     return gemma_generate(c, w, g, prompt_embeds, force_ids, out_ids, (bf16_t*)step_logits, ws, ws_bytes, st);
   if (gen_sample_validate("generate", c->vocab, g->do_sample, g->top_k, g->temperature,
@@ -1328,9 +1307,24 @@ int ptk_gemma3_generate_penalized(const ptk_gemma3_config* c, const ptk_gemma3_w
   if (!ws || ws_bytes < base + 256) return set_error("generate: workspace too small");
   int32_t* status = pen_status_word(ws, base);
   CK(launch_zero(status, 16, st));
-  CK(gemma_generate(c, w, g, prompt_embeds, force_ids, out_ids, (bf16_t*)step_logits, ws, base, st,
-                    repetition_penalty, status));
+  CK(gemma_generate(c, w, g, prompt_embeds, force_ids, out_ids, (bf16_t*)step_logits, ws, base, st, pa.penalty,
+                    status));
   return pen_status_check("generate", status, st);
+}
+
+int ptk_gemma3_generate(const ptk_gemma3_config* c, const ptk_gemma3_weights* w, const ptk_gemma3_generate_desc* g,
+                        const float* prompt_embeds, const int64_t* force_ids, int64_t* out_ids, void* step_logits,
+                        void* ws, size_t ws_bytes, void* stream) {
+  return generate_entry(c, w, g, prompt_embeds, force_ids, out_ids, step_logits, nullptr, ws, ws_bytes,
+                        (hipStream_t)stream);
+}
+
+int ptk_gemma3_generate_penalized(const ptk_gemma3_config* c, const ptk_gemma3_weights* w,
+                                  const ptk_gemma3_generate_desc* g, const float* prompt_embeds,
+                                  const int64_t* force_ids, int64_t* out_ids, void* step_logits,
+                                  float repetition_penalty, void* ws, size_t ws_bytes, void* stream) {
+  return generate_entry(c, w, g, prompt_embeds, force_ids, out_ids, step_logits, &repetition_penalty, ws, ws_bytes,
+                        (hipStream_t)stream);
 }
 
 int ptk_bf16_sumsq_partial_floats(void) { return scale_sumsq_partial_floats(); }

@@ -444,9 +444,6 @@ int launch_fill_normal_bf16(bf16_t* out, long n, uint64_t seed, float std, float
 int launch_gen_prompt(const float* src, long ld_b, int B, int P, int Pp, int H, float* x, int32_t* kv, hipStream_t st);
 int launch_kv_append(const bf16_t* src, long src_z, bf16_t* dst, long dst_z, int Z, int p0, int n, int D,
                      hipStream_t st);
-int launch_gen_sample(const bf16_t* logits, long ld, int B, int V, int do_sample, int top_k, float temperature,
-                      float top_p, uint64_t seed, int step, long eos_id, long pad_id, int32_t* finished, int64_t* out,
-                      long ld_out, int64_t* next, hipStream_t st);
 // skinny GEMM of the decode steps (gemm_skinny.hip): M <= 64 rows, N % 64, K % 32; ACT_NONE / ACT_GEGLU, bf16 out
 bool skinny_supported(int M, int N, int K, long lda, long ldb, long ldc, int act);
 size_t skinny_part_bytes(int M, int N, int K);
@@ -472,6 +469,7 @@ struct PenArgs {
   float penalty;
   int32_t* status;
 };
+constexpr PenArgs kNoPen{nullptr, 0, 0, 1.f, nullptr};   // no penalty
 inline bool pen_active(const PenArgs& pa) { return pa.n_hist > 0 && pa.penalty != 1.f; }
 int pen_validate(const char* who, const PenArgs& pa);                  // the penalty's arguments alone
 // every host-side rule of a sampling step / a beam selection, penalised or not (no device call); a penalised beam
@@ -481,18 +479,16 @@ int gen_sample_validate(const char* who, int V, int do_sample, int top_k, float 
 int beam_candidates_validate(int batch, int K, int V, int do_sample, int top_k, float top_p, float temperature,
                              int min_keep, int n_cand, const void* ws, size_t ws_bytes, const PenArgs& pa);
 int pen_status_check(const char* who, int32_t* status, hipStream_t st);
-int launch_gen_sample_pen(const bf16_t* logits, long ld, int B, int V, int do_sample, int top_k, float temperature,
-                          float top_p, uint64_t seed, int step, long eos_id, long pad_id, int32_t* finished,
-                          int64_t* out, long ld_out, int64_t* next, const PenArgs& pa, hipStream_t st);
-int launch_beam_candidates_pen(const bf16_t* logits, long ld, const float* beam_scores, int batch, int K, int V,
-                               int do_sample, int top_k, float top_p, float temperature, int min_keep, uint64_t seed,
-                               int step, int n_cand, int64_t* tok, int32_t* beam, float* score, void* ws,
-                               size_t ws_bytes, const PenArgs& pa, hipStream_t st);
+// one sampling step / one beam selection (its per-row candidates, then beam_merge_kernel): validated by the
+// functions above, then the penalised kernel when pen_active(pa) (pa.status required), else the plain one
+int launch_gen_sample(const bf16_t* logits, long ld, int B, int V, int do_sample, int top_k, float temperature,
+                      float top_p, uint64_t seed, int step, long eos_id, long pad_id, int32_t* finished, int64_t* out,
+                      long ld_out, int64_t* next, const PenArgs& pa, hipStream_t st);
 size_t beam_candidates_ws_bytes(int batch, int K, int n_cand);
 int launch_beam_candidates(const bf16_t* logits, long ld, const float* beam_scores, int batch, int K, int V,
                            int do_sample, int top_k, float top_p, float temperature, int min_keep, uint64_t seed,
                            int step, int n_cand, int64_t* tok, int32_t* beam, float* score, void* ws,
-                           size_t ws_bytes, hipStream_t st);
+                           size_t ws_bytes, const PenArgs& pa, hipStream_t st);
 
 // ---- unfrozen-LLM step (train.hip) ----
 // out [cols][rows_pad] bf16 = in[map(r)][c] (r < rows), zero for rows <= r < rows_pad
