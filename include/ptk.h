@@ -308,6 +308,17 @@ size_t ptk_projector_workspace_bytes(const ptk_projector* p, int rows);
 int ptk_projector_bwd(const ptk_projector* p, int rows, const void* x, const void* a, const void* h,
                       const void* dy, float* dw1, float* db1, float* dw2, float* db2, void* ws, size_t ws_bytes,
                       void* stream);
+/* Stage 2's trainable projector (Stage2/trainer.py:214-223,336-337 under --mixed_precision bf16: bf16
+ * parameters and a bf16 .grad).  dy bf16 [rows, Dl]; dw1 [I,Dv], db1 [I], dw2 [Dl,I], db2 [Dl]: bf16, ACCUMULATED
+ * as bf16(grad + bf16(G)) with G = colsum(dy), dy^T h, colsum(dA), dA^T x and dA = bf16((dy W2) gelu'(a)), each
+ * contraction in fp32.  The weight grads run as ptk_weight_grad_bf16 (the TN GEMM where rows % 64 == 0, the
+ * transposed NT path otherwise, with p->tail_ws as their fp32 scratch), the bias grads' accumulate is the last
+ * level of the column reduction.  No input grad (the vision tower is frozen).  No floating-point atomics: a
+ * repeated call from the same state is bit-identical.  Dv, I, Dl multiples of 8; ws 16-byte aligned. */
+size_t ptk_projector_bwd_bf16_workspace_bytes(const ptk_projector* p, int rows);
+int ptk_projector_bwd_bf16(const ptk_projector* p, int rows, const void* x, const void* a, const void* h,
+                           const void* dy, void* dw1, void* db1, void* dw2, void* db2, void* ws, size_t ws_bytes,
+                           void* stream);
 /* dy[(b,i)] = bf16(dx_llm[b*seq_pad + i - 1]) (i >= 1), 0 for i == 0 (the dropped patch). */
 int ptk_gather_vision_grad(const float* dx_llm, int batch, int num_patches, int seq_pad, int llm_dim, void* dy,
                            void* stream);

@@ -188,6 +188,9 @@ SIGNATURES = {
                                   c_int64, c_int, c_void_p]),
     "ptk_projector_workspace_bytes": (c_size_t, [C.POINTER(ProjectorC), c_int]),
     "ptk_projector_bwd": (c_int, [C.POINTER(ProjectorC), c_int] + [c_void_p] * 8 + [c_void_p, c_size_t, c_void_p]),
+    "ptk_projector_bwd_bf16_workspace_bytes": (c_size_t, [C.POINTER(ProjectorC), c_int]),
+    "ptk_projector_bwd_bf16": (c_int, [C.POINTER(ProjectorC), c_int] + [c_void_p] * 8 +
+                               [c_void_p, c_size_t, c_void_p]),
     "ptk_gather_vision_grad": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p]),
     "ptk_gemma3_workspace_bytes": (c_size_t, [C.POINTER(Gemma3ConfigC), c_int, c_int, c_int]),
     "ptk_gemma3_loss_fwd_bwd": (c_int, [C.POINTER(Gemma3ConfigC), C.POINTER(Gemma3WeightsC),

@@ -338,6 +338,63 @@ int ptk_projector_bwd(const ptk_projector* p, int rows, const void* x, const voi
   return projector_bwd_stage(p, rows, x, a, h, dy, dw1, db1, dw2, db2, ws, ws_bytes, 1, ST);
 }
 
+// Stage 2's trainable projector (bf16 parameters and .grad, Stage2/trainer.py:214-223,336-337 under
+// --mixed_precision bf16): the four grads ACCUMULATED as autograd does into a bf16 .grad, bf16(grad + bf16(G)).
+// Workspace: dA | ta | tb (the NT path's transposed operands) | the column sums' partials.
+size_t ptk_projector_bwd_bf16_workspace_bytes(const ptk_projector* p, int rows) {
+  if (!p || rows <= 0) return 0;
+  const size_t Dv = p->vision_dim, I = p->inter_dim, Dl = p->llm_dim, R = ((size_t)rows + 63) / 64 * 64;
+  size_t s = 0;
+  s += align256(R * I * 2);                       // dA
+  s += align256((I > Dl ? I : Dl) * R * 2);       // ta: dy^T, then dA^T
+  s += align256((I > Dv ? I : Dv) * R * 2);       // tb: h^T, then x^T
+  s += align256(64 * (I > Dl ? I : Dl) * 4);      // colsum partials
+  return s;
+}
+
+int ptk_projector_bwd_bf16(const ptk_projector* p, int rows, const void* x, const void* a, const void* h,
+                           const void* dy, void* dw1, void* db1, void* dw2, void* db2, void* ws, size_t ws_bytes,
+                           void* stream) {
+  if (!p || !x || !a || !h || !dy || !dw1 || !db1 || !dw2 || !db2 || !ws)
+    return set_error("projector_bwd_bf16: null argument");
+  if (!p->w2t) return set_error("projector_bwd_bf16: the projector has no W2^T");
+  const int Dv = p->vision_dim, I = p->inter_dim, Dl = p->llm_dim, R = rows;
+  if (R <= 0 || Dv <= 0 || I <= 0 || Dl <= 0) return set_error("projector_bwd_bf16: rows %d dims %d %d %d", R, Dv, I, Dl);
+  if (Dv % 8 || I % 8 || Dl % 8) return set_error("projector_bwd_bf16: dims %d %d %d must be multiples of 8", Dv, I, Dl);
+  if (ws_bytes < ptk_projector_bwd_bf16_workspace_bytes(p, rows)) return set_error("projector_bwd_bf16: workspace too small");
+  if ((uintptr_t)ws & 15) return set_error("projector_bwd_bf16: workspace must be 16-byte aligned");
+  const size_t Rp = ((size_t)R + 63) / 64 * 64;
+  char* w = (char*)ws;
+  bf16_t* dA = (bf16_t*)w; w += align256(Rp * I * 2);
+  bf16_t* ta = (bf16_t*)w; w += align256((size_t)(I > Dl ? I : Dl) * Rp * 2);
+  bf16_t* tb = (bf16_t*)w; w += align256((size_t)(I > Dv ? I : Dv) * Rp * 2);
+  float* cpart = (float*)w;
+  const long cpart_floats = 64L * (I > Dl ? I : Dl);
+  // the weight grads' fp32 scratch (stream-K slabs of the TN GEMM, K slices of the NT one): the projector's tail
+  // scratch, which this call's GEMMs use one after the other on the stream
+  float* part = (float*)p->tail_ws;
+  const int64_t part_floats = part ? (int64_t)(p8_tail_scratch_bytes() / sizeof(float)) : 0;
+  // rows a multiple of 64 (B x 576 patches in a real run): the TN GEMM on the token-major operands in place;
+  // a ragged row count: the transposed, zero-padded copies for the NT GEMMs
+  const int mode = R % 64 == 0 ? 0 : 1;
+  StageScope stage("projector.bwd", ST);
+  // db2 += colsum(dy); dW2 += dy^T . h
+  if (launch_colsum_bf16_acc((const bf16_t*)dy, R, Dl, (bf16_t*)db2, cpart, cpart_floats, ST)) return -1;
+  if (ptk_weight_grad_bf16(dy, Dl, 0, 0, 0, Dl, h, I, 0, 0, 0, I, R, dw2, ta, tb, part, part_floats, mode, stream))
+    return -1;
+  // dA = bf16((dy . W2) * gelu'(a))
+  GemmArgs g2;
+  g2.A = (const bf16_t*)dy; g2.B = (const bf16_t*)p->w2t; g2.C = dA; g2.M = R; g2.N = I; g2.K = Dl;
+  g2.lda = Dl; g2.ldb = Dl; g2.ldc = I; g2.aux_in = (const bf16_t*)a; g2.ld_aux_in = I;
+  {   // (the tail scratch is lent to this GEMM alone: the weight grads hold it as `part`)
+    TailScratchScope tail(p->tail_ws, ST);
+    if (tail.status || launch_gemm(g2, ACT_GELU_ERF_BWD, OUT_BF16, 1, ST)) return -1;
+  }
+  // db1 += colsum(dA); dW1 += dA^T . x
+  if (launch_colsum_bf16_acc(dA, R, I, (bf16_t*)db1, cpart, cpart_floats, ST)) return -1;
+  return ptk_weight_grad_bf16(dA, I, 0, 0, 0, I, x, Dv, 0, 0, 0, Dv, R, dw1, ta, tb, part, part_floats, mode, stream);
+}
+
 int ptk_gather_vision_grad(const float* dx_llm, int batch, int num_patches, int seq_pad, int llm_dim, void* dy,
                            void* stream) {
   return launch_gather_dy(dx_llm, batch, num_patches, seq_pad, llm_dim, (bf16_t*)dy, ST);

@@ -388,9 +388,13 @@ __global__ void __launch_bounds__(64) colsum_partial_kernel(const bf16_t* __rest
   *reinterpret_cast<float4*>(pp + 4) = make_float4(s[4], s[5], s[6], s[7]);
 }
 // stage 2: 8 threads per column, thread g summing chunks g, g + 8, ... (8 loads in flight), then the 8 sums in
-// g order through LDS
+// g order through LDS.  out f32: the sum, overwritten (Stage 1's fp32 grads); out bf16: the same last level stores
+// bf16(out + bf16(sum)), autograd's accumulate into a bf16 .grad (Stage 2's trainable projector) -- no pass of its own
+PTK_DEV void colsum_store(float* o, float t) { *o = t; }
+PTK_DEV void colsum_store(bf16_t* o, float t) { *o = f2bf(bf2f(*o) + bfround(t)); }
+template <typename TO>
 __global__ void __launch_bounds__(256) colsum_final_kernel(const float* __restrict__ partial, int cols, int chunks,
-                                                           float* __restrict__ out) {
+                                                           TO* __restrict__ out) {
   __shared__ float red[8][33];
   const int cl = threadIdx.x & 31, g = threadIdx.x >> 5;
   const int c = blockIdx.x * 32 + cl;
@@ -412,13 +416,15 @@ __global__ void __launch_bounds__(256) colsum_final_kernel(const float* __restri
     float t = 0.f;
 #pragma unroll
     for (int j = 0; j < 8; ++j) t += red[j][cl];
-    out[c] = t;
+    colsum_store(out + c, t);
   }
 }
-int launch_colsum_bf16(const bf16_t* x, int rows, int cols, float* out, float* partial, long part_floats,
-                       hipStream_t st) {
+template <typename TO>
+static int colsum_bf16_t(const bf16_t* x, int rows, int cols, TO* out, float* partial, long part_floats,
+                         hipStream_t st) {
   if (cols % 8 || ((uintptr_t)x & 15) || ((uintptr_t)partial & 15)) return set_error("colsum: cols %% 8 / alignment");
   if (rows <= 0 || cols <= 0) return 0;
+  if (part_floats < cols) return set_error("colsum: partial scratch of %ld floats for %d columns", part_floats, cols);
   const int lanes = cols / 8, blocks_x = (lanes + 63) / 64;
   long chunks = std::max<long>(1, std::min<long>(4096 / blocks_x, (rows + 15) / 16));
   chunks = std::max<long>(1, std::min<long>(chunks, part_floats / cols));
@@ -426,8 +432,16 @@ int launch_colsum_bf16(const bf16_t* x, int rows, int cols, float* out, float* p
   chunks = (rows + per - 1) / per;
   hipLaunchKernelGGL(colsum_partial_kernel, dim3((unsigned)blocks_x, (unsigned)chunks), dim3(64), 0, st, x, rows, cols,
                      per, partial);
-  hipLaunchKernelGGL(colsum_final_kernel, dim3((cols + 31) / 32), dim3(256), 0, st, partial, cols, (int)chunks, out);
+  hipLaunchKernelGGL(colsum_final_kernel<TO>, dim3((cols + 31) / 32), dim3(256), 0, st, partial, cols, (int)chunks, out);
   RET_OK("colsum");
+}
+int launch_colsum_bf16(const bf16_t* x, int rows, int cols, float* out, float* partial, long part_floats,
+                       hipStream_t st) {
+  return colsum_bf16_t(x, rows, cols, out, partial, part_floats, st);
+}
+int launch_colsum_bf16_acc(const bf16_t* x, int rows, int cols, bf16_t* grad, float* partial, long part_floats,
+                           hipStream_t st) {
+  return colsum_bf16_t(x, rows, cols, grad, partial, part_floats, st);
 }
 
 // ---------------------------------------------------------------- grad norm + clip + AdamW

@@ -430,6 +430,9 @@ int launch_loss_reduce(const float* row_loss, int R, const float* count, float* 
 int launch_gather_dy(const float* dx, int B, int N, int Spad, int H, bf16_t* dy, hipStream_t st);
 int launch_colsum_bf16(const bf16_t* x, int rows, int cols, float* out, float* partial, long part_floats,
                        hipStream_t st);
+// the same column sums accumulated into a bf16 .grad: grad[c] = bf16(grad[c] + bf16(sum)) in the last level
+int launch_colsum_bf16_acc(const bf16_t* x, int rows, int cols, bf16_t* grad, float* partial, long part_floats,
+                           hipStream_t st);
 int launch_sumsq_partial(const float* x, long n, float* partial, int nparts, hipStream_t st);
 int launch_clip_adamw(float* p, const float* g, float* m, float* v, long n, const float* partial,
                       int nparts, float grad_scale, float max_norm, float lr, float b1, float b2,

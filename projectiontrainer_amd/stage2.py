@@ -1,4 +1,10 @@
-"""Stage 2 (VQA fine-tune, BASELINE cfg4) on MI355X: the unfrozen Gemma3 step.
+"""Stage 2 (VQA fine-tune) on MI355X: the Gemma3 step with the LLM and / or the projector trained.
+
+Three of the reference's Stage-2 modes run here (the vision tower is frozen in all; QLoRA is not supported):
+  A  --unfreeze_llm                                   (BASELINE cfg4; the default)   AdamW over the LLM
+  B  --unfreeze_llm --unfreeze_projection_layer                                      AdamW over LLM + projector
+  C  --unfreeze_projection_layer (LLM frozen)                                        AdamW over the projector
+Mode A is described first; the trainable projector of B and C follows below.
 
 The body of `with self.accelerator.accumulate(...)` in VQATrainerStage2.train
 (Stage2/trainer.py:299-444) with the cfg4 flags (`--unfreeze_llm`; projector
@@ -23,6 +29,22 @@ same layout.  Under `--mixed_precision bf16` the reference loads the LLM in bf16
 store keeps exactly that (no fp32 master copy), and the optimizer rounds every tensor op to bf16 as
 torch's AdamW does on bf16 parameters.  The transposed copies the dX GEMMs read and the fp32 copies of the
 norm weights the norm kernels read are refreshed after each optimizer step.
+
+Trainable projector (Stage2/trainer.py:214-223 collects its parameters, :336-337 runs it with grad; modes B, C).
+`train_vqa_stage2.py:274` casts it to bf16 under `--mixed_precision bf16`, so its parameters, grads and moments are
+bf16 too: `ProjectorTrainState` holds [W1 | b1 | W2 | b2] in one flat bf16 store (a second one for the grads, two
+for the moments), rounded once from the module it is given.  Per micro-batch, after the Gemma3 call:
+  dy = bf16(dx[vision rows]), patch 0's row zero          ptk_gather_vision_grad
+  db2, dW2, dA = bf16((dy W2) gelu'(a)), db1, dW1         ptk_projector_bwd_bf16: each G rounded once to bf16 and
+                                                          accumulated as autograd does, bf16(grad + bf16(G))
+The forward is the frozen projector's (ptk_projector_fwd, bf16 GEMMs, output rounded to bf16), reading W1 / W2 from
+the store; W2^T and the fp32 biases it takes are refreshed after each step.  The optimizer step clips each module
+on its own norm (:437-439) and applies ptk_adamw_bf16 to both with the shared LR / step count.  The projector
+store is replicated, not sharded: at world > 1 its grads are summed by one all-reduce (44 MB of bf16 at 22 M
+parameters, next to the LLM's 2 GB reduce-scatter), scaled by 1 / world before the sum of squares, and every rank
+takes the same deterministic step, so the replicas stay bit-identical without a parameter exchange.
+Mode C builds no Gemma3TrainState: the LLM keeps the k-step-tiled frozen weights it was built with and runs
+ptk_gemma3_loss_fwd_bwd (loss and dX only, label_offset = the question length).
 """
 from __future__ import annotations
 
@@ -43,6 +65,7 @@ NORM_KEYS = ("ln_in", "ln_post_attn", "ln_pre_ff", "ln_post_ff", "q_norm", "k_no
 HF_NORM = {"ln_in": "input_layernorm", "ln_post_attn": "post_attention_layernorm",
            "ln_pre_ff": "pre_feedforward_layernorm", "ln_post_ff": "post_feedforward_layernorm",
            "q_norm": "self_attn.q_norm", "k_norm": "self_attn.k_norm"}
+PROJ_KEYS = ("model.0.weight", "model.0.bias", "model.2.weight", "model.2.bias")   # Stage1/projectors.py's names
 
 
 def deinterleave_gate_up(wgu):
@@ -154,14 +177,77 @@ class Gemma3TrainState:
         return sd
 
 
+class ProjectorTrainState:
+    """Flat bf16 parameter / grad / moment store of a trainable Stage-2 projector.
+
+    Under `--mixed_precision bf16` the reference casts the projector (train_vqa_stage2.py:274), so its parameters,
+    grads and AdamW moments are bf16 tensors: the store holds [W1 | b1 | W2 | b2] (each segment 128-B aligned, the
+    gaps zero) rounded from whatever the module holds, the grads in a second buffer of the same layout, and no
+    fp32 master.  The kernels read W1 and W2 from the store itself; W2^T (the dA GEMM's operand) and the fp32
+    biases ptk_projector_fwd takes are derived copies, refreshed after each optimizer step.  Stage 1's
+    MLPProjector (fp32 masters, `flat` / `flat_grad`) is only read here, never changed."""
+
+    ALIGN = 64   # elements
+
+    def __init__(self, proj: MLPProjector, device):
+        Dv, I, Dl = proj.vision_dim, proj.inter_dim, proj.llm_dim
+        self.dims = (Dv, I, Dl)
+        off, self.offsets = 0, {}
+        for name, shape in zip(PROJ_KEYS, ((I, Dv), (I,), (Dl, I), (Dl,))):
+            self.offsets[name] = (off, shape)
+            off += (math.prod(shape) + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+        self.numel = off
+        bf = torch.bfloat16
+        self.flat = torch.zeros(off, dtype=bf, device=device)
+        self.grad = torch.zeros(off, dtype=bf, device=device)
+        self.exp_avg = torch.zeros(off, dtype=bf, device=device)
+        self.exp_avg_sq = torch.zeros(off, dtype=bf, device=device)
+        for name, p in zip(PROJ_KEYS, (proj.w1, proj.b1, proj.w2, proj.b2)):
+            K.cast_bf16(p.detach().to(device=device, dtype=torch.float32).contiguous(), self.view(name))
+        self.w2t = torch.empty((I, Dl), dtype=bf, device=device)
+        self.bias32 = torch.zeros(I + Dl, dtype=torch.float32, device=device)
+        self.tail = torch.zeros(L.lib().ptk_gemm_tail_scratch_bytes(), dtype=torch.uint8, device=device)
+        self.sumsq = torch.zeros(1, dtype=torch.float32, device=device)
+        self.c = L.ProjectorC(Dv, I, Dl, self.view(PROJ_KEYS[0]).data_ptr(), self.bias32.data_ptr(),
+                              self.view(PROJ_KEYS[2]).data_ptr(), self.bias32[I:].data_ptr(), self.w2t.data_ptr(),
+                              self.tail.data_ptr())
+        self.refresh()
+
+    def view(self, name, buf=None):
+        off, shape = self.offsets[name]
+        return (self.flat if buf is None else buf)[off:off + math.prod(shape)].view(shape)
+
+    def refresh(self):
+        """Derived copies the kernels read: W2^T and the fp32 biases."""
+        I = self.dims[1]
+        K.transpose(self.view(PROJ_KEYS[2]), out=self.w2t)
+        self.bias32[:I].copy_(self.view(PROJ_KEYS[1]))
+        self.bias32[I:].copy_(self.view(PROJ_KEYS[3]))
+
+    def state_dict(self, grads=False):
+        """The reference's names (Stage1/projectors.py: model.0.weight, model.0.bias, model.2.weight,
+        model.2.bias), bf16 tensors on the device (views of the store)."""
+        return {k: self.view(k, self.grad if grads else None) for k in PROJ_KEYS}
+
+
 class Stage2Engine:
-    """One VQATrainerStage2 micro-batch (forward_backward) and optimizer step (optimizer_step)."""
+    """One VQATrainerStage2 micro-batch (forward_backward) and optimizer step (optimizer_step).
+
+    train_llm / train_projector select the reference's Stage-2 modes (the vision tower is frozen in all):
+      A  train_llm=True,  train_projector=False   ptk_gemma3_train_fwd_bwd; AdamW over the LLM (the default)
+      B  train_llm=True,  train_projector=True    the same, then ptk_projector_bwd_bf16; AdamW over both
+      C  train_llm=False, train_projector=True    ptk_gemma3_loss_fwd_bwd (dX only, the LLM as it was built --
+                                                  frozen, with its k-step-tiled weights; no Gemma3TrainState),
+                                                  then ptk_projector_bwd_bf16; AdamW over the projector"""
 
     def __init__(self, vision: SiglipVisionTower, llm: Gemma3CausalLM, projector: MLPProjector, *,
                  learning_rate=1e-4, weight_decay=0.01, gradient_accumulation_steps=1, max_grad_norm=1.0,
                  warmup_steps=0, total_steps=1, betas=(0.9, 0.999), eps=1e-8, world_size=1, rank=0,
-                 process_group=None, pad_token_id=None, zero1=None):
+                 process_group=None, pad_token_id=None, zero1=None, train_llm=True, train_projector=False):
+        if not train_llm and not train_projector:
+            raise ValueError("No trainable parameters found. Stage2Engine needs train_llm or train_projector")
         self.vision, self.llm, self.proj = vision, llm, projector
+        self.train_llm, self.train_projector = bool(train_llm), bool(train_projector)
         self.device = vision.device
         self.lr0, self.wd, self.gas, self.max_norm = learning_rate, weight_decay, gradient_accumulation_steps, max_grad_norm
         self.warmup, self.total, self.betas, self.eps = warmup_steps, total_steps, betas, eps
@@ -174,13 +260,19 @@ class Stage2Engine:
             # the optimizer step exchanges grads only through the reduce-scatter / all-gather of ZeRO-1; without
             # it every rank would update from its own grads and the replicas would drift apart
             raise ValueError("Stage2Engine: zero1=False is not supported with world_size > 1")
-        self.state = Gemma3TrainState(llm, world_size)
-        o, n = self.state.shard(rank)
+        # a frozen LLM (mode C) keeps the weights it was built with: no flat store, no grads, no moments
+        self.state = Gemma3TrainState(llm, world_size) if self.train_llm else None
+        o, n = self.state.shard(rank) if self.train_llm else (0, 0)
         self.shard_lo, self.shard_n = o, n
         self.exp_avg = torch.zeros(n, dtype=torch.bfloat16, device=self.device)
         self.exp_avg_sq = torch.zeros(n, dtype=torch.bfloat16, device=self.device)
-        self._shard_grad = torch.empty(n, dtype=torch.bfloat16, device=self.device) if self.zero1 else None
-        self._shard_param = torch.empty(n, dtype=torch.bfloat16, device=self.device) if self.zero1 else None
+        shards = self.zero1 and self.train_llm
+        self._shard_grad = torch.empty(n, dtype=torch.bfloat16, device=self.device) if shards else None
+        self._shard_param = torch.empty(n, dtype=torch.bfloat16, device=self.device) if shards else None
+        # a trained projector (modes B, C): its own bf16 store, replicated on every rank (22 M parameters next to
+        # the LLM's 1 B: its grads are all-reduced whole and every rank takes the same AdamW step)
+        self.pstate = ProjectorTrainState(projector, self.device) if self.train_projector else None
+        self.proj_grad_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._partial = torch.empty(L.lib().ptk_bf16_sumsq_partial_floats(), dtype=torch.float32, device=self.device)
         self.sumsq = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -205,7 +297,14 @@ class Stage2Engine:
         self.x = torch.empty((B * Sp, Dl), dtype=torch.float32, device=dev)
         self.dx = torch.empty((B * Sp, Dl), dtype=torch.float32, device=dev)
         self.vision.workspace(B)
-        n = L.lib().ptk_gemma3_train_workspace_bytes(self.llm.c_cfg, B, T, Sp)
+        if self.pstate is not None:
+            self.dy = torch.empty((B * N, Dl), dtype=bf, device=dev)
+            nb = L.lib().ptk_projector_bwd_bf16_workspace_bytes(self.pstate.c, B * N)
+            if getattr(self, "_proj_ws", None) is None or self._proj_ws.numel() < nb:
+                self._proj_ws = None
+                self._proj_ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+        ws_bytes = L.lib().ptk_gemma3_train_workspace_bytes if self.train_llm else L.lib().ptk_gemma3_workspace_bytes
+        n = ws_bytes(self.llm.c_cfg, B, T, Sp)
         if getattr(self, "_ws", None) is None or self._ws.numel() < n:
             self._ws = None
             self._ws = torch.empty(n, dtype=torch.uint8, device=dev)
@@ -225,7 +324,13 @@ class Stage2Engine:
         else:
             K.cast_bf16(pixel_values.contiguous(), self.px)
         self.vision.forward_into(self.px, self.vis)
-        self.proj.fwd_into(self.vis, self.a, self.h, self.x, out_map=(self.N, 1, self.Sp, -1), round_bf16=True)
+        if self.pstate is None:
+            self.proj.fwd_into(self.vis, self.a, self.h, self.x, out_map=(self.N, 1, self.Sp, -1), round_bf16=True)
+        else:   # the same forward from the engine's bf16 store (the parameters the optimizer updates)
+            L.check(L.lib().ptk_projector_fwd(self.pstate.c, self.vis.shape[0], self.vis.data_ptr(),
+                                              self.a.data_ptr(), self.h.data_ptr(), self.x.data_ptr(),
+                                              L.RowMap(self.N, 1, self.Sp, -1), self.x.shape[1], 1,
+                                              L.stream_ptr(self.device)), "ptk_projector_fwd")
         ids = torch.cat([question_ids, answer_ids], dim=1).contiguous()
         labels = answer_ids.masked_fill(answer_ids == self.pad_token_id, -100).contiguous()
         cfg = self.llm.c_cfg
@@ -241,9 +346,23 @@ class Stage2Engine:
         """One micro-batch: loss (device [1], the mean CE over answer tokens) and grads accumulated
         (scaled 1/gas^2: the trainer's loss / gas and Accelerator.backward's / gas)."""
         cfg, bt = self._inputs(pixel_values, question_ids, answer_ids)
-        L.check(L.lib().ptk_gemma3_train_fwd_bwd(cfg, self.llm.c_w, bt, self.state.c_grads, self._ws.data_ptr(),
-                                                 self._ws.numel(), L.stream_ptr(self.device)),
-                "ptk_gemma3_train_fwd_bwd")
+        stream = L.stream_ptr(self.device)
+        if self.train_llm:
+            L.check(L.lib().ptk_gemma3_train_fwd_bwd(cfg, self.llm.c_w, bt, self.state.c_grads, self._ws.data_ptr(),
+                                                     self._ws.numel(), stream), "ptk_gemma3_train_fwd_bwd")
+        else:   # frozen LLM: loss and dX only
+            L.check(L.lib().ptk_gemma3_loss_fwd_bwd(cfg, self.llm.c_w, bt, self._ws.data_ptr(), self._ws.numel(),
+                                                    stream), "ptk_gemma3_loss_fwd_bwd")
+        if self.pstate is not None:
+            # dy = bf16(dx[vision rows]) (patch 0's row zero), then the four grads accumulated into the bf16 .grad
+            ps, B = self.pstate, question_ids.shape[0]
+            L.check(L.lib().ptk_gather_vision_grad(self.dx.data_ptr(), B, self.N, self.Sp, self.x.shape[1],
+                                                   self.dy.data_ptr(), stream), "gather_vision_grad")
+            g = ps.state_dict(grads=True)
+            L.check(L.lib().ptk_projector_bwd_bf16(ps.c, B * self.N, self.vis.data_ptr(), self.a.data_ptr(),
+                                                   self.h.data_ptr(), self.dy.data_ptr(),
+                                                   *[g[k].data_ptr() for k in PROJ_KEYS], self._proj_ws.data_ptr(),
+                                                   self._proj_ws.numel(), stream), "ptk_projector_bwd_bf16")
         return self.loss
 
     def forward_loss(self, pixel_values, question_ids, answer_ids):
@@ -254,7 +373,20 @@ class Stage2Engine:
         return self.loss
 
     def optimizer_step(self):
-        """DDP grad average (ZeRO-1 reduce-scatter), clip_grad_norm_(max_norm), AdamW, all-gather, schedule."""
+        """DDP grad average (ZeRO-1 reduce-scatter), clip_grad_norm_(max_norm), AdamW, all-gather, schedule.
+        The LLM (when trained) and the projector (when trained) are clipped each on its own norm
+        (Stage2/trainer.py:437-439) and share the LR, betas, eps, weight decay and step count."""
+        lr = self.lr0 * cosine_lambda(self.sched_step, self.warmup, self.total)
+        self.opt_step += 1
+        if self.train_llm:
+            self._llm_step(lr)
+        if self.pstate is not None:
+            self._projector_step(lr)
+        self.sched_step += self.world
+        self.last_lr = lr       # the LR this optimizer step used (param_groups[0]["lr"] during .step())
+        return lr
+
+    def _llm_step(self, lr):
         st, stream = self.state, L.stream_ptr(self.device)
         lo, n = self.shard_lo, self.shard_n
         if self.zero1:
@@ -266,8 +398,6 @@ class Stage2Engine:
                                                   self.sumsq.data_ptr(), stream), "grad_scale_sumsq")
         if self.zero1:
             dist.all_reduce(self.sumsq, op=dist.ReduceOp.SUM, group=self.pg)
-        lr = self.lr0 * cosine_lambda(self.sched_step, self.warmup, self.total)
-        self.opt_step += 1
         b1, b2 = self.betas
         p = st.flat[lo:lo + n]
         L.check(L.lib().ptk_adamw_bf16(p.data_ptr(), g.data_ptr(), self.exp_avg.data_ptr(),
@@ -279,9 +409,26 @@ class Stage2Engine:
             all_gather_(st.flat, self._shard_param, self.world, self.pg)
         st.refresh()
         st.zero_grad()
-        self.sched_step += self.world
-        self.last_lr = lr       # the LR this optimizer step used (param_groups[0]["lr"] during .step())
-        return lr
+
+    def _projector_step(self, lr):
+        """The projector's own clip + AdamW on its whole store: at world > 1 the ranks' grads are summed by one
+        all-reduce (every rank receives the same bits), scaled by 1 / world before the sum of squares as the
+        LLM's shards are, and every rank takes the same deterministic step, so the replicas stay bit-identical
+        without a parameter exchange."""
+        ps, stream = self.pstate, L.stream_ptr(self.device)
+        scale = 1.0
+        if self.zero1:
+            all_reduce_sum_(ps.grad, self.pg)
+            scale = 1.0 / self.world
+        L.check(L.lib().ptk_bf16_grad_scale_sumsq(ps.grad.data_ptr(), ps.numel, scale, self._partial.data_ptr(),
+                                                  ps.sumsq.data_ptr(), stream), "grad_scale_sumsq")
+        b1, b2 = self.betas
+        L.check(L.lib().ptk_adamw_bf16(ps.flat.data_ptr(), ps.grad.data_ptr(), ps.exp_avg.data_ptr(),
+                                       ps.exp_avg_sq.data_ptr(), ps.numel, ps.sumsq.data_ptr(), self.max_norm, lr,
+                                       b1, b2, self.eps, self.wd, self.opt_step, self.proj_grad_norm.data_ptr(),
+                                       stream), "adamw_bf16")
+        ps.refresh()
+        ps.grad.zero_()
 
     @property
     def scheduler_lr(self):
@@ -294,24 +441,45 @@ class Stage2Engine:
     def optimizer_state(self):
         """This rank's optimizer shard (moments of params [shard_lo, shard_lo + shard_n) of the flat store)
         plus the step / schedule counters: every rank's file together is the full AdamW state."""
-        return {"exp_avg": self.exp_avg.cpu(), "exp_avg_sq": self.exp_avg_sq.cpu(), "step": self.opt_step,
-                "sched_step": self.sched_step, "shard": (self.shard_lo, self.shard_n), "world": self.world,
-                "rank": self.rank, "numel": self.state.numel}
+        sd = {"exp_avg": self.exp_avg.cpu(), "exp_avg_sq": self.exp_avg_sq.cpu(), "step": self.opt_step,
+              "sched_step": self.sched_step, "shard": (self.shard_lo, self.shard_n), "world": self.world,
+              "rank": self.rank, "numel": self._llm_numel}
+        if self.pstate is not None:   # the projector's moments, whole on every rank (its store is replicated)
+            sd.update(proj_exp_avg=self.pstate.exp_avg.cpu(), proj_exp_avg_sq=self.pstate.exp_avg_sq.cpu(),
+                      proj_numel=self.pstate.numel)
+        return sd
+
+    @property
+    def _llm_numel(self):
+        return self.state.numel if self.train_llm else 0
 
     def load_optimizer_state(self, sd):
-        if (sd["world"], sd["rank"], sd["numel"]) != (self.world, self.rank, self.state.numel):
-            raise ValueError(f"optimizer shard of world {sd['world']} rank {sd['rank']} (store {sd['numel']}) does "
-                             f"not match this engine (world {self.world} rank {self.rank} store {self.state.numel})")
+        pn = self.pstate.numel if self.pstate is not None else 0
+        if (sd["world"], sd["rank"], sd["numel"], sd.get("proj_numel", 0)) != (self.world, self.rank,
+                                                                              self._llm_numel, pn):
+            raise ValueError(f"optimizer shard of world {sd['world']} rank {sd['rank']} (store {sd['numel']}, "
+                             f"projector {sd.get('proj_numel', 0)}) does not match this engine (world {self.world} "
+                             f"rank {self.rank} store {self._llm_numel}, projector {pn})")
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
+        if self.pstate is not None:
+            self.pstate.exp_avg.copy_(sd["proj_exp_avg"])
+            self.pstate.exp_avg_sq.copy_(sd["proj_exp_avg_sq"])
         self.opt_step, self.sched_step = int(sd["step"]), int(sd["sched_step"])
+
+    def projector_state_dict(self, grads=False):
+        """The trained projector's parameters (or accumulated grads) under the reference's names, bf16 on the
+        device -- what Gemma3TrainState.state_dict_hf is for the LLM."""
+        if self.pstate is None:
+            raise ValueError("Stage2Engine: the projector is frozen (train_projector=False)")
+        return self.pstate.state_dict(grads)
 
 
 def synthetic_engine(cfg, device="cuda", seed=0, **kw):
     """Stage2Engine over random-init towers of the named architecture (benchmark; no checkpoints offline)."""
     vision = SiglipVisionTower.random_init(cfg.vision, device, seed)
     llm = Gemma3CausalLM.random_init(cfg.text, device, seed + 1, max_pos=Gemma3CausalLM.seq_pad(cfg.seq_len),
-                                     frozen=False)   # trained here: no k-step-tiled copies
+                                     frozen=not kw.get("train_llm", True))   # trained: no k-step-tiled copies
     torch.manual_seed(seed + 2)
     proj = MLPProjector(cfg.vision.hidden_size, cfg.text.hidden_size, cfg.expansion_factor, device=device)
     return Stage2Engine(vision, llm, proj, **kw)
@@ -328,6 +496,17 @@ def reduce_scatter_(out_shard, flat, world, rank, group=None):
     else:
         dist.reduce_scatter_tensor(out_shard, flat, op=dist.ReduceOp.SUM, group=group)
     return out_shard
+
+
+def all_reduce_sum_(t, group=None):
+    """Sum of the bf16 tensor `t` over ranks, in place: the same bits on every rank."""
+    if dist.get_backend(group) == "gloo":
+        f = t.float()               # gloo has no bf16 sum: fp32 sum of the bf16 values, one rounding
+        dist.all_reduce(f, op=dist.ReduceOp.SUM, group=group)
+        t.copy_(f)
+    else:
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t
 
 
 def all_gather_(flat, shard, world, group=None):

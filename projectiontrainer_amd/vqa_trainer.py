@@ -3,10 +3,14 @@ running its step on libptk (`stage2.Stage2Engine`).
 
 Same constructor signature, `.train()`, `.evaluate(epoch, global_step)`,
 `.save_model(path)` and the module-level `vqa_collate_fn(batch, tokenizer)`.
-Supported configuration: BASELINE cfg4 — the LLM unfrozen (`freeze_llm=False`,
-no QLoRA), projector and vision encoder frozen; anything else raises
-NotImplementedError (QLoRA/peft needs 4-bit kernels; a trainable vision
-encoder or projector needs their backward passes).  Note that the reference's
+Supported configurations (the vision encoder frozen, no QLoRA):
+  A  freeze_llm=False, freeze_projection_layer=True   BASELINE cfg4 (`--unfreeze_llm`)
+  B  freeze_llm=False, freeze_projection_layer=False  + `--unfreeze_projection_layer`: LLM and projector trained
+  C  freeze_llm=True,  freeze_projection_layer=False  the projector alone, over a frozen LLM
+`freeze_llm=True` with `freeze_projection_layer=True` raises the reference's ValueError ("No trainable
+parameters found", Stage2/trainer.py:242-243); `enable_qlora`, an unfrozen vision encoder and
+`train_ve_first_epoch` raise NotImplementedError (QLoRA/peft needs 4-bit kernels; a trainable vision
+encoder needs its backward pass).  Every flag is checked before any device work.  Note that the reference's
 own run script ships `ENABLE_QLORA=true` (`Stage2/run_vqa_train_stage2.sh:42`,
 a Qwen3-8B QLoRA run); cfg4 -- the benchmark this path is built for -- is the
 unfrozen-LLM form of the same trainer (`--unfreeze_llm`, `UNFREEZE_LLM` in that
@@ -18,7 +22,8 @@ Kept reference semantics (Stage2/trainer.py:248-488):
   * `accelerator.accumulate`: an optimizer step when (micro+1) % gas == 0 or at
     the end of the rank's loader; loss / gas before `backward`, which divides by
     gas again (SURVEY F7), grads summed over micro-batches;
-  * clip_grad_norm_(llm, 1.0), AdamW(lr, wd) over the LLM parameters, cosine
+  * clip_grad_norm_(module, 1.0) for each trained module on its own (:437-439),
+    AdamW(lr, wd) over the trained parameters (LLM, then projector), cosine
     schedule with warmup (horizon from the unsharded loader), stepped
     num_processes times per optimizer step;
   * logging keys `train/batch_loss` (every micro-batch), `train/step_loss` (sync
@@ -30,10 +35,13 @@ do_sample=True, num_beams=3, top_p=0.9, top_k=50)` on libptk's stepwise KV-cache
 (`Gemma3CausalLM.beam_generate`), decoded and written to `validation_examples/epoch_{n}_examples.txt` and
 `all_validation_examples.txt` in the reference's format (at most 20 examples, gathered over the ranks).  `save_model` writes the fine-tuned LLM as HF-named
 bf16 tensors (`language_model/model.safetensors`, accelerate's save_model
-layout) plus the optimizer state of this rank (`optimizer_rank{r}.pt`).
+layout) when the LLM was trained, the trained projector as `projection_layer/model.safetensors` (bf16, the
+reference's four keys) + `projection_layer/projector_config.json` (what the reference's
+`load_pretrained_projector` reads), plus the optimizer state of this rank (`optimizer_rank{r}.pt`).
 """
 from __future__ import annotations
 
+import json
 import logging
 import math
 import os
@@ -74,12 +82,16 @@ class VQATrainerStage2:
                  wandb_project: str, log_fn=None, seed: int = 0, generate_max_new_tokens: int = 512,
                  generate_num_beams: int = 3, generate_do_sample: bool = True, generate_top_k: int = 50,
                  generate_top_p: float = 0.9, generate_seed: int = 0):
+        # every flag check before any device work
         if enable_qlora:
             raise NotImplementedError("VQATrainerStage2 (HIP): QLoRA / 4-bit LLMs are not supported; run with the "
-                                      "dense bf16 LLM and --unfreeze_llm")
-        if freeze_llm or not freeze_projection_layer or not freeze_vision_encoder or train_ve_first_epoch:
-            raise NotImplementedError("VQATrainerStage2 (HIP) supports the BASELINE cfg4 setting: LLM unfrozen, "
-                                      "projector and vision encoder frozen")
+                                      "dense bf16 LLM and --unfreeze_llm and / or --unfreeze_projection_layer")
+        if not freeze_vision_encoder or train_ve_first_epoch:
+            raise NotImplementedError("VQATrainerStage2 (HIP): the vision encoder stays frozen (a trainable SigLIP "
+                                      "needs its backward pass); train the LLM and / or the projector")
+        if freeze_llm and freeze_projection_layer:   # Stage2/trainer.py:242-243
+            raise ValueError("No trainable parameters found. Check freezing configuration and QLoRA setup.")
+        self.train_llm, self.train_projector = not freeze_llm, not freeze_projection_layer
         if accelerator is None:
             accelerator = D.DistState(gradient_accumulation_steps)
         elif not isinstance(accelerator, D.DistState):
@@ -102,7 +114,7 @@ class VQATrainerStage2:
         self.vision_encoder = vision_encoder if isinstance(vision_encoder, SiglipVisionTower) \
             else SiglipVisionTower.from_hf(vision_encoder, self.device)
         self.language_model = language_model if isinstance(language_model, Gemma3CausalLM) \
-            else Gemma3CausalLM.from_hf(language_model, self.device, max_pos=4096, frozen=False)
+            else Gemma3CausalLM.from_hf(language_model, self.device, max_pos=4096, frozen=freeze_llm)
         if not isinstance(projection_layer, MLPProjector):
             sd = projection_layer.state_dict()
             p = MLPProjector(sd["model.0.weight"].shape[1], sd["model.2.weight"].shape[0])
@@ -120,7 +132,8 @@ class VQATrainerStage2:
                                    gradient_accumulation_steps=gradient_accumulation_steps,
                                    warmup_steps=self.num_warmup_steps, total_steps=self.max_train_steps,
                                    world_size=acc.num_processes, rank=acc.process_index,
-                                   pad_token_id=-1 if pad is None else int(pad))
+                                   pad_token_id=-1 if pad is None else int(pad),
+                                   train_llm=self.train_llm, train_projector=self.train_projector)
         self.global_step = 0
 
     # ------------------------------------------------------------------ data
@@ -248,23 +261,42 @@ class VQATrainerStage2:
             logger.error("Failed to save validation examples to file: %s", e, exc_info=True)
 
     def save_model(self, path):
-        """Called on EVERY rank.  Main process: language_model/model.safetensors (HF names, bf16) and the
-        tokenizer (Stage2/trainer.py:740-742).  Every rank: optimizer_rank{r}.pt with its ZeRO-1 shard of the
-        AdamW moments and the step / schedule counters, so the files of all ranks hold the complete optimizer
-        state that the reference's accelerator.save_state writes (:718); load with load_optimizer_state."""
+        """Called on EVERY rank.  Main process, following Stage2/trainer.py:721-769: when the LLM was trained,
+        language_model/model.safetensors (HF names, bf16) and the tokenizer (:730-742); when the projector was
+        trained, projection_layer/model.safetensors (bf16 tensors under model.0.weight, model.0.bias,
+        model.2.weight, model.2.bias: accelerate's save_model layout) and projection_layer/projector_config.json
+        ({"vision_dim", "llm_dim"}, indent 4) -- the pair the reference's load_pretrained_projector reads.  The
+        trained values are also loaded back into `self.projection_layer`.  Every rank: optimizer_rank{r}.pt
+        with its ZeRO-1 shard of the LLM's AdamW moments, the projector's moments (replicated) and the step /
+        schedule counters, so the files of all ranks hold the complete optimizer state that the reference's
+        accelerator.save_state writes (:718); load with load_optimizer_state."""
         acc = self.accelerator
         os.makedirs(path, exist_ok=True)
         torch.cuda.synchronize(self.device)
         torch.save(self.engine.optimizer_state(), os.path.join(path, f"optimizer_rank{acc.process_index}.pt"))
         if acc.is_main_process:
             from safetensors.torch import save_file
-            llm_dir = os.path.join(path, "language_model")
-            os.makedirs(llm_dir, exist_ok=True)
-            sd = {k: v.detach().contiguous().cpu() for k, v in self.engine.state.state_dict_hf().items()}
-            save_file(sd, os.path.join(llm_dir, "model.safetensors"))
-            if hasattr(self.tokenizer, "save_pretrained"):
-                self.tokenizer.save_pretrained(llm_dir)
-            logger.info("Full language model saved to %s", llm_dir)
+            if self.train_llm:
+                llm_dir = os.path.join(path, "language_model")
+                os.makedirs(llm_dir, exist_ok=True)
+                sd = {k: v.detach().contiguous().cpu() for k, v in self.engine.state.state_dict_hf().items()}
+                save_file(sd, os.path.join(llm_dir, "model.safetensors"))
+                if hasattr(self.tokenizer, "save_pretrained"):
+                    self.tokenizer.save_pretrained(llm_dir)
+                logger.info("Full language model saved to %s", llm_dir)
+            else:
+                logger.info("Language model was frozen and not saved.")
+        if self.train_projector:
+            sd = {k: v.detach().contiguous().cpu() for k, v in self.engine.projector_state_dict().items()}
+            self.projection_layer.load_state_dict({k: v.float() for k, v in sd.items()})   # (bf16 -> fp32: exact)
+            if acc.is_main_process:
+                proj_dir = os.path.join(path, "projection_layer")
+                os.makedirs(proj_dir, exist_ok=True)
+                save_file(sd, os.path.join(proj_dir, "model.safetensors"))
+                with open(os.path.join(proj_dir, "projector_config.json"), "w") as f:
+                    json.dump({"vision_dim": self.projection_layer.vision_dim,
+                               "llm_dim": self.projection_layer.llm_dim}, f, indent=4)
+                logger.info("Projection layer saved to %s", proj_dir)
         acc.wait_for_everyone()
 
     def load_optimizer_state(self, path):
