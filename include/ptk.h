@@ -67,7 +67,8 @@ typedef struct {
   int64_t ld_rowadd;
   const float* resid;
   int64_t ld_resid;
-  void* aux;                 /* GELU_ERF: pre-activation out; GEGLU: a = bf16(gelu_tanh(gate)) out */
+  void* aux;                 /* GELU_ERF, GELU_TANH (optional; ld_aux == ldc, identity cmap): bf16 pre-activation out;
+                                GEGLU: a = bf16(gelu_tanh(gate)) out */
   void* aux2;                /* GEGLU: b = bf16(gelu_tanh'(gate) * up) out (h = bf16(a * up) is C) */
   int64_t ld_aux;
   const void* aux_in;        /* GELU_ERF_BWD: pre-activation; GEGLU_BWD: the forward's a (du = bf16(dh) * a) */
@@ -287,6 +288,64 @@ int ptk_siglip_fwd(const ptk_siglip_config* c, const ptk_siglip_weights* w, int 
                    void* out, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------ *
+ * SigLIP vision tower, trained (Stage 2 with the vision encoder unfrozen:   *
+ * Stage2/trainer.py:214-237,267-289; Stage 0 trains the same tower).        *
+ * ptk_siglip_train_fwd is ptk_siglip_fwd -- the same launches, a            *
+ * bit-identical `out` -- that keeps in the workspace what the backward      *
+ * reads: the im2col patches and, per layer, the residual stream at layer    *
+ * entry and after attention, q|k|v, the attention output, the flash LSE,    *
+ * the fc1 pre-activation and the GELU output (the LN outputs are            *
+ * recomputed).  ptk_siglip_bwd then takes d_out bf16 [B*N, D], the grad of  *
+ * `out`, from the SAME workspace and ACCUMULATES every parameter's grad     *
+ * into caller-owned bf16 buffers shaped like ptk_siglip_weights,            *
+ * bf16(grad + bf16(G)) as autograd does into a bf16 .grad (the reference    *
+ * loads the tower in bf16 under --mixed_precision bf16,                     *
+ * train_vqa_stage2.py:141-153).  Rounding points: bf16 autograd of the bf16 *
+ * module -- every tensor handed between ops is bf16, every contraction and  *
+ * every LayerNorm / GELU derivative fp32.  The key projections' bias grads  *
+ * are exactly zero for every input (softmax does not see a key bias) and   *
+ * nothing is added to them.  d(pixels) is not computed.  The                *
+ * weights are read row-major: the *_kt copies in the layer structs are      *
+ * copies of frozen weights and are ignored by both calls.  No               *
+ * floating-point atomics: a repeated call from the same state is            *
+ * bit-identical.  Refused before any launch: num_patches % 64 != 0 (the     *
+ * flash backward takes whole 64-row blocks), head_dim != 64, a workspace    *
+ * below ptk_siglip_train_workspace_bytes.                                   *
+ * ------------------------------------------------------------------------ */
+typedef struct {
+  void* wqkv; void* bqkv; void* wo; void* bo; void* w1; void* b1; void* w2; void* b2;   /* bf16, ptk_siglip_layer's shapes */
+  void* ln1_w; void* ln1_b; void* ln2_w; void* ln2_b;
+} ptk_siglip_layer_grads;
+
+typedef struct {
+  void* patch_w; void* patch_b; void* pos; void* post_w; void* post_b;   /* bf16, ptk_siglip_weights' shapes */
+  const ptk_siglip_layer_grads* layers;   /* HOST array [layers] */
+} ptk_siglip_grads;
+
+size_t ptk_siglip_train_workspace_bytes(const ptk_siglip_config* c, int batch);
+int ptk_siglip_train_fwd(const ptk_siglip_config* c, const ptk_siglip_weights* w, int batch, const void* pixels,
+                         void* out, void* ws, size_t ws_bytes, void* stream);
+int ptk_siglip_bwd(const ptk_siglip_config* c, const ptk_siglip_weights* w, int batch, const void* d_out,
+                   const ptk_siglip_grads* g, void* ws, size_t ws_bytes, void* stream);
+
+/* The backward's side kernels (unit-test surface; ptk_siglip_bwd calls the same launchers).
+ * ptk_layernorm_bwd_bf16: x, dy bf16 [rows, cols], w f32 [cols]; dx bf16 = bf16(dacc + dLN/dx) with dacc bf16 NULL or
+ * == dx (mean and rstd recomputed from x in fp32); dw, db (bf16 [cols], both or neither) accumulated as bf16(grad +
+ * bf16(G)), G = colsum(dy xhat) / colsum(dy) from fp32 per-workgroup partials summed in a fixed order; partial:
+ * ptk_layernorm_bwd_partial_floats(rows, cols) floats (unused without dw / db).  cols % 8 == 0, cols <= 2048.
+ * ptk_gelu_tanh_bwd_bf16: dpre = bf16(dg * gelu_tanh'(pre)) over packed bf16 [rows, cols] (dpre may be dg).
+ * ptk_colsum_bf16_acc: grad[c] = bf16(grad[c] + bf16(sum_r x[r][c])), the bias grads' two-level column reduction
+ * (ptk_projector_bwd_bf16's); partial >= cols floats, more let more workgroups share the rows.
+ * ptk_pos_grad_bf16: dpos[n] = bf16(dpos[n] + bf16(sum_b dh0[b N + n])), b in index order. */
+int64_t ptk_layernorm_bwd_partial_floats(int rows, int cols);
+int ptk_layernorm_bwd_bf16(const void* x, const float* w, const void* dy, const void* dacc, void* dx, int rows,
+                           int cols, float eps, void* dw, void* db, float* partial, int64_t part_floats, void* stream);
+int ptk_gelu_tanh_bwd_bf16(const void* dg, const void* pre, void* dpre, int64_t rows, int cols, void* stream);
+int ptk_colsum_bf16_acc(const void* x, int rows, int cols, void* grad, float* partial, int64_t part_floats,
+                        void* stream);
+int ptk_pos_grad_bf16(const void* dh0, int batch, int num_patches, int hidden, void* dpos, void* stream);
+
+/* ------------------------------------------------------------------------ *
  * MLPProjector (Stage1/projectors.py:13-29): Linear -> GELU(erf) -> Linear  *
  * ------------------------------------------------------------------------ */
 typedef struct {
@@ -313,12 +372,21 @@ int ptk_projector_bwd(const ptk_projector* p, int rows, const void* x, const voi
  * as bf16(grad + bf16(G)) with G = colsum(dy), dy^T h, colsum(dA), dA^T x and dA = bf16((dy W2) gelu'(a)), each
  * contraction in fp32.  The weight grads run as ptk_weight_grad_bf16 (the TN GEMM where rows % 64 == 0, the
  * transposed NT path otherwise, with p->tail_ws as their fp32 scratch), the bias grads' accumulate is the last
- * level of the column reduction.  No input grad (the vision tower is frozen).  No floating-point atomics: a
+ * level of the column reduction.  No input grad (ptk_projector_input_grad adds it).  No floating-point atomics: a
  * repeated call from the same state is bit-identical.  Dv, I, Dl multiples of 8; ws 16-byte aligned. */
 size_t ptk_projector_bwd_bf16_workspace_bytes(const ptk_projector* p, int rows);
 int ptk_projector_bwd_bf16(const ptk_projector* p, int rows, const void* x, const void* a, const void* h,
                            const void* dy, void* dw1, void* db1, void* dw2, void* db2, void* ws, size_t ws_bytes,
                            void* stream);
+/* ptk_projector_bwd_bf16 that also yields the projector's input grad for a trained vision tower: dx_vis bf16
+ * [rows, Dv] = bf16(dA W1), with the one dA = bf16((dy W2) gelu'(a)) the parameter grads use.  dw1, db1, dw2, db2:
+ * all given (the projector is trained as well: the same launches and the same four results as
+ * ptk_projector_bwd_bf16) or all NULL (frozen projector: only dA and dx_vis are computed).  W1^T is transposed
+ * into the workspace on every call, so nothing derived from a trained W1 can go stale. */
+size_t ptk_projector_input_grad_workspace_bytes(const ptk_projector* p, int rows);
+int ptk_projector_input_grad(const ptk_projector* p, int rows, const void* x, const void* a, const void* h,
+                             const void* dy, void* dw1, void* db1, void* dw2, void* db2, void* dx_vis, void* ws,
+                             size_t ws_bytes, void* stream);
 /* dy[(b,i)] = bf16(dx_llm[b*seq_pad + i - 1]) (i >= 1), 0 for i == 0 (the dropped patch). */
 int ptk_gather_vision_grad(const float* dx_llm, int batch, int num_patches, int seq_pad, int llm_dim, void* dy,
                            void* stream);

@@ -76,6 +76,16 @@ class SiglipWeightsC(C.Structure):
                 ("post_w", c_void_p), ("post_b", c_void_p), ("layers", C.POINTER(SiglipLayerC))]
 
 
+class SiglipLayerGradsC(C.Structure):
+    _fields_ = [(n, c_void_p) for n in ("wqkv", "bqkv", "wo", "bo", "w1", "b1", "w2", "b2",
+                                        "ln1_w", "ln1_b", "ln2_w", "ln2_b")]
+
+
+class SiglipGradsC(C.Structure):
+    _fields_ = [("patch_w", c_void_p), ("patch_b", c_void_p), ("pos", c_void_p), ("post_w", c_void_p),
+                ("post_b", c_void_p), ("layers", C.POINTER(SiglipLayerGradsC))]
+
+
 class ProjectorC(C.Structure):
     _fields_ = [("vision_dim", c_int), ("inter_dim", c_int), ("llm_dim", c_int),
                 ("w1", c_void_p), ("b1", c_void_p), ("w2", c_void_p), ("b2", c_void_p), ("w2t", c_void_p),
@@ -184,6 +194,20 @@ SIGNATURES = {
     "ptk_siglip_workspace_bytes": (c_size_t, [C.POINTER(SiglipConfigC), c_int]),
     "ptk_siglip_fwd": (c_int, [C.POINTER(SiglipConfigC), C.POINTER(SiglipWeightsC), c_int, c_void_p, c_void_p,
                                c_void_p, c_size_t, c_void_p]),
+    "ptk_siglip_train_workspace_bytes": (c_size_t, [C.POINTER(SiglipConfigC), c_int]),
+    "ptk_siglip_train_fwd": (c_int, [C.POINTER(SiglipConfigC), C.POINTER(SiglipWeightsC), c_int, c_void_p, c_void_p,
+                                     c_void_p, c_size_t, c_void_p]),
+    "ptk_siglip_bwd": (c_int, [C.POINTER(SiglipConfigC), C.POINTER(SiglipWeightsC), c_int, c_void_p,
+                               C.POINTER(SiglipGradsC), c_void_p, c_size_t, c_void_p]),
+    "ptk_layernorm_bwd_partial_floats": (c_int64, [c_int, c_int]),
+    "ptk_layernorm_bwd_bf16": (c_int, [c_void_p] * 5 + [c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_int64,
+                                       c_void_p]),
+    "ptk_gelu_tanh_bwd_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "ptk_colsum_bf16_acc": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ptk_pos_grad_bf16": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "ptk_projector_input_grad_workspace_bytes": (c_size_t, [C.POINTER(ProjectorC), c_int]),
+    "ptk_projector_input_grad": (c_int, [C.POINTER(ProjectorC), c_int] + [c_void_p] * 9 +
+                                 [c_void_p, c_size_t, c_void_p]),
     "ptk_projector_fwd": (c_int, [C.POINTER(ProjectorC), c_int, c_void_p, c_void_p, c_void_p, c_void_p, RowMap,
                                   c_int64, c_int, c_void_p]),
     "ptk_projector_workspace_bytes": (c_size_t, [C.POINTER(ProjectorC), c_int]),

@@ -111,6 +111,27 @@ int ptk_gemm_skinny(const void* A, int64_t lda, const void* B, int64_t ldb, void
                             act, (float*)part, part_bytes, (hipStream_t)stream);
 }
 
+int64_t ptk_layernorm_bwd_partial_floats(int rows, int cols) {
+  return rows > 0 && cols > 0 ? (int64_t)layernorm_bwd_partial_floats(rows, cols) : 0;
+}
+int ptk_layernorm_bwd_bf16(const void* x, const float* w, const void* dy, const void* dacc, void* dx, int rows,
+                           int cols, float eps, void* dw, void* db, float* partial, int64_t part_floats,
+                           void* stream) {
+  return launch_layernorm_bwd_bf16((const bf16_t*)x, w, (const bf16_t*)dy, (const bf16_t*)dacc, (bf16_t*)dx, rows,
+                                   cols, eps, (bf16_t*)dw, (bf16_t*)db, partial, (long)part_floats, ST);
+}
+int ptk_gelu_tanh_bwd_bf16(const void* dg, const void* pre, void* dpre, int64_t rows, int cols, void* stream) {
+  return launch_gelu_tanh_bwd_bf16((const bf16_t*)dg, (const bf16_t*)pre, (bf16_t*)dpre, (long)rows, cols, ST);
+}
+int ptk_colsum_bf16_acc(const void* x, int rows, int cols, void* grad, float* partial, int64_t part_floats,
+                        void* stream) {
+  if (!x || !grad || !partial) return set_error("colsum_bf16_acc: null argument");
+  return launch_colsum_bf16_acc((const bf16_t*)x, rows, cols, (bf16_t*)grad, partial, (long)part_floats, ST);
+}
+int ptk_pos_grad_bf16(const void* dh0, int batch, int num_patches, int hidden, void* dpos, void* stream) {
+  return launch_pos_grad_bf16((const bf16_t*)dh0, batch, num_patches, hidden, (bf16_t*)dpos, ST);
+}
+
 int ptk_layernorm(const float* x, const float* w, const float* b, void* y, int rows, int cols, float eps,
                   void* stream) {
   return launch_layernorm(x, w, b, (bf16_t*)y, rows, cols, eps, ST);
@@ -352,17 +373,15 @@ size_t ptk_projector_bwd_bf16_workspace_bytes(const ptk_projector* p, int rows) 
   return s;
 }
 
-int ptk_projector_bwd_bf16(const ptk_projector* p, int rows, const void* x, const void* a, const void* h,
-                           const void* dy, void* dw1, void* db1, void* dw2, void* db2, void* ws, size_t ws_bytes,
-                           void* stream) {
-  if (!p || !x || !a || !h || !dy || !dw1 || !db1 || !dw2 || !db2 || !ws)
-    return set_error("projector_bwd_bf16: null argument");
-  if (!p->w2t) return set_error("projector_bwd_bf16: the projector has no W2^T");
+}  // extern "C"
+
+// ptk_projector_bwd_bf16 and ptk_projector_input_grad.  grads: the four parameter grads are accumulated (the
+// trained projector); dx_vis != null: the input grad bf16(dA W1) as well, W1^T transposed into w1t first
+static int projector_bwd_bf16_run(const ptk_projector* p, int rows, const void* x, const void* a, const void* h,
+                                  const void* dy, void* dw1, void* db1, void* dw2, void* db2, void* dx_vis,
+                                  void* ws, bf16_t* w1t, void* stream) {
+  const bool grads = dw1 != nullptr;
   const int Dv = p->vision_dim, I = p->inter_dim, Dl = p->llm_dim, R = rows;
-  if (R <= 0 || Dv <= 0 || I <= 0 || Dl <= 0) return set_error("projector_bwd_bf16: rows %d dims %d %d %d", R, Dv, I, Dl);
-  if (Dv % 8 || I % 8 || Dl % 8) return set_error("projector_bwd_bf16: dims %d %d %d must be multiples of 8", Dv, I, Dl);
-  if (ws_bytes < ptk_projector_bwd_bf16_workspace_bytes(p, rows)) return set_error("projector_bwd_bf16: workspace too small");
-  if ((uintptr_t)ws & 15) return set_error("projector_bwd_bf16: workspace must be 16-byte aligned");
   const size_t Rp = ((size_t)R + 63) / 64 * 64;
   char* w = (char*)ws;
   bf16_t* dA = (bf16_t*)w; w += align256(Rp * I * 2);
@@ -378,10 +397,12 @@ int ptk_projector_bwd_bf16(const ptk_projector* p, int rows, const void* x, cons
   // a ragged row count: the transposed, zero-padded copies for the NT GEMMs
   const int mode = R % 64 == 0 ? 0 : 1;
   StageScope stage("projector.bwd", ST);
-  // db2 += colsum(dy); dW2 += dy^T . h
-  if (launch_colsum_bf16_acc((const bf16_t*)dy, R, Dl, (bf16_t*)db2, cpart, cpart_floats, ST)) return -1;
-  if (ptk_weight_grad_bf16(dy, Dl, 0, 0, 0, Dl, h, I, 0, 0, 0, I, R, dw2, ta, tb, part, part_floats, mode, stream))
-    return -1;
+  if (grads) {
+    // db2 += colsum(dy); dW2 += dy^T . h
+    if (launch_colsum_bf16_acc((const bf16_t*)dy, R, Dl, (bf16_t*)db2, cpart, cpart_floats, ST)) return -1;
+    if (ptk_weight_grad_bf16(dy, Dl, 0, 0, 0, Dl, h, I, 0, 0, 0, I, R, dw2, ta, tb, part, part_floats, mode, stream))
+      return -1;
+  }
   // dA = bf16((dy . W2) * gelu'(a))
   GemmArgs g2;
   g2.A = (const bf16_t*)dy; g2.B = (const bf16_t*)p->w2t; g2.C = dA; g2.M = R; g2.N = I; g2.K = Dl;
@@ -390,9 +411,60 @@ int ptk_projector_bwd_bf16(const ptk_projector* p, int rows, const void* x, cons
     TailScratchScope tail(p->tail_ws, ST);
     if (tail.status || launch_gemm(g2, ACT_GELU_ERF_BWD, OUT_BF16, 1, ST)) return -1;
   }
-  // db1 += colsum(dA); dW1 += dA^T . x
-  if (launch_colsum_bf16_acc(dA, R, I, (bf16_t*)db1, cpart, cpart_floats, ST)) return -1;
-  return ptk_weight_grad_bf16(dA, I, 0, 0, 0, I, x, Dv, 0, 0, 0, Dv, R, dw1, ta, tb, part, part_floats, mode, stream);
+  if (grads) {
+    // db1 += colsum(dA); dW1 += dA^T . x
+    if (launch_colsum_bf16_acc(dA, R, I, (bf16_t*)db1, cpart, cpart_floats, ST)) return -1;
+    if (ptk_weight_grad_bf16(dA, I, 0, 0, 0, I, x, Dv, 0, 0, 0, Dv, R, dw1, ta, tb, part, part_floats, mode, stream))
+      return -1;
+  }
+  if (!dx_vis) return 0;
+  // dx_vis = bf16(dA . W1): W1 [I, Dv] -> W1^T [Dv, I], the K-contiguous B of the NT GEMM
+  if (launch_transpose((const bf16_t*)p->w1, Dv, 0, 0, 1, w1t, I, 0, 0, 1, I, Dv, I, ST)) return -1;
+  GemmArgs g3;
+  g3.A = dA; g3.B = w1t; g3.C = dx_vis; g3.M = R; g3.N = Dv; g3.K = I; g3.lda = I; g3.ldb = I; g3.ldc = Dv;
+  TailScratchScope tail(p->tail_ws, ST);
+  if (tail.status) return -1;
+  return launch_gemm(g3, ACT_NONE, OUT_BF16, 1, ST);
+}
+
+extern "C" {
+
+int ptk_projector_bwd_bf16(const ptk_projector* p, int rows, const void* x, const void* a, const void* h,
+                           const void* dy, void* dw1, void* db1, void* dw2, void* db2, void* ws, size_t ws_bytes,
+                           void* stream) {
+  if (!p || !x || !a || !h || !dy || !dw1 || !db1 || !dw2 || !db2 || !ws)
+    return set_error("projector_bwd_bf16: null argument");
+  if (!p->w2t) return set_error("projector_bwd_bf16: the projector has no W2^T");
+  const int Dv = p->vision_dim, I = p->inter_dim, Dl = p->llm_dim, R = rows;
+  if (R <= 0 || Dv <= 0 || I <= 0 || Dl <= 0) return set_error("projector_bwd_bf16: rows %d dims %d %d %d", R, Dv, I, Dl);
+  if (Dv % 8 || I % 8 || Dl % 8) return set_error("projector_bwd_bf16: dims %d %d %d must be multiples of 8", Dv, I, Dl);
+  if (ws_bytes < ptk_projector_bwd_bf16_workspace_bytes(p, rows)) return set_error("projector_bwd_bf16: workspace too small");
+  if ((uintptr_t)ws & 15) return set_error("projector_bwd_bf16: workspace must be 16-byte aligned");
+  return projector_bwd_bf16_run(p, rows, x, a, h, dy, dw1, db1, dw2, db2, nullptr, ws, nullptr, stream);
+}
+
+// Workspace: ptk_projector_bwd_bf16's, then W1^T
+size_t ptk_projector_input_grad_workspace_bytes(const ptk_projector* p, int rows) {
+  if (!p || rows <= 0) return 0;
+  return ptk_projector_bwd_bf16_workspace_bytes(p, rows) + align256((size_t)p->vision_dim * p->inter_dim * 2);
+}
+
+int ptk_projector_input_grad(const ptk_projector* p, int rows, const void* x, const void* a, const void* h,
+                             const void* dy, void* dw1, void* db1, void* dw2, void* db2, void* dx_vis, void* ws,
+                             size_t ws_bytes, void* stream) {
+  if (!p || !a || !dy || !dx_vis || !ws) return set_error("projector_input_grad: null argument");
+  const bool grads = dw1 || db1 || dw2 || db2;
+  if (grads && (!dw1 || !db1 || !dw2 || !db2 || !x || !h))
+    return set_error("projector_input_grad: the four parameter grads (with x and h) go together, or all NULL");
+  if (!p->w1 || !p->w2t) return set_error("projector_input_grad: the projector has no W1 / W2^T");
+  const int Dv = p->vision_dim, I = p->inter_dim, Dl = p->llm_dim, R = rows;
+  if (R <= 0 || Dv <= 0 || I <= 0 || Dl <= 0) return set_error("projector_input_grad: rows %d dims %d %d %d", R, Dv, I, Dl);
+  if (Dv % 64 || I % 64 || Dl % 64)
+    return set_error("projector_input_grad: dims %d %d %d must be multiples of 64", Dv, I, Dl);
+  if (ws_bytes < ptk_projector_input_grad_workspace_bytes(p, rows)) return set_error("projector_input_grad: workspace too small");
+  if ((uintptr_t)ws & 15) return set_error("projector_input_grad: workspace must be 16-byte aligned");
+  bf16_t* w1t = (bf16_t*)((char*)ws + ptk_projector_bwd_bf16_workspace_bytes(p, rows));
+  return projector_bwd_bf16_run(p, rows, x, a, h, dy, dw1, db1, dw2, db2, dx_vis, ws, w1t, stream);
 }
 
 int ptk_gather_vision_grad(const float* dx_llm, int batch, int num_patches, int seq_pad, int llm_dim, void* dy,

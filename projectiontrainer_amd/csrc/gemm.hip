@@ -796,6 +796,9 @@ int launch_gemm(const GemmArgs& a, int act, int out, int batch, hipStream_t st, 
   const long ntile = (long)((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
   if (ntile > 0x7fffffffL) return set_error("gemm: too many tiles");
   if (!gemm_act_out(act, out, [](auto, auto) {})) return set_error("gemm: unsupported (act=%d, out=%d)", act, out);
+  // the GELU-tanh epilogues store the pre-activation at C's own offsets (the persistent ones address it through C's)
+  if (act == ACT_GELU_TANH && a.aux && (a.ld_aux != a.ldc || a.cmap.g != 0 || a.cmap.off != 0))
+    return set_error("gemm: a GELU-tanh pre-activation output needs ld_aux == ldc and an identity C row map");
   const GemmPlan plan = planned ? *planned : gemm_plan(a, act, out, batch, gemm_plan_env());
   // k-step-tiled activations are the operands' contract: no family but the one with the variant may run them
   if (a.a_kt && !a_ktiled_ok(a, plan, act, out, batch, lean_epilogue_enabled()))

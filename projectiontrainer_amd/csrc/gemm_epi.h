@@ -37,8 +37,12 @@ PTK_DEV void epi_vec4(const GemmArgs& p, char* Cz, long r, long c, float4 v) {
     v.x += b.x; v.y += b.y; v.z += b.z; v.w += b.w;
   }
   if constexpr (ACT == ACT_GELU_TANH) {
+    // (aux: the bf16 pre-activation kept for the backward, the trained SigLIP tower's fc1)
 #pragma unroll
-    for (int e = 0; e < 4; ++e) el(v, e) = gelu_tanh(bfround(el(v, e)));
+    for (int e = 0; e < 4; ++e) el(v, e) = bfround(el(v, e));
+    if (p.aux) stbf4(p.aux + r * p.ld_aux + c, v);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) el(v, e) = gelu_tanh(el(v, e));
   } else if constexpr (ACT == ACT_GELU_ERF) {
     // pre-activation kept (bf16) for the backward: Stage1/projectors.py:17-18
 #pragma unroll
@@ -104,7 +108,10 @@ PTK_DEV void epi_vec8_bf16(const GemmArgs& p, char* Cz, long r, long c, float4 v
   }
   if constexpr (ACT == ACT_GELU_TANH) {
 #pragma unroll
-    for (int e = 0; e < 8; ++e) v[e] = gelu_tanh(bfround(v[e]));
+    for (int e = 0; e < 8; ++e) v[e] = bfround(v[e]);
+    if (p.aux) stbf8(p.aux + r * p.ld_aux + c, v);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = gelu_tanh(v[e]);
   } else if constexpr (ACT == ACT_GELU_ERF) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = bfround(v[e]);
@@ -140,7 +147,9 @@ PTK_DEV void epi_scalar(const GemmArgs& p, char* Cz, long r, long c, float v) {
   if (p.bf16_linear) v = bfround(v);
   if (p.rowadd) v += p.rowadd[(r % p.rowadd_period) * p.ld_rowadd + c];
   if constexpr (ACT == ACT_GELU_TANH) {
-    v = gelu_tanh(bfround(v));
+    v = bfround(v);
+    if (p.aux) p.aux[r * p.ld_aux + c] = f2bf(v);
+    v = gelu_tanh(v);
   } else if constexpr (ACT == ACT_GELU_ERF) {
     float a = bfround(v);
     if (p.aux) p.aux[r * p.ld_aux + c] = f2bf(a);

@@ -96,6 +96,8 @@ PTK_DEV W4Row w4_row(const GemmArgs& p, long r) {
   return w;
 }
 
+PTK_DEV const GemmArgs& kernarg_args();   // (below: the kernel's own arguments behind a laundered pointer)
+
 // 8 consecutive columns [c, c+8) of one row (c % 8 == 0); rows r >= M, unmapped rows and columns
 // c >= N store into the sink
 template <int ACT, int OUT, bool STORE = true>
@@ -114,6 +116,15 @@ PTK_DEV void w4_epi8(const GemmArgs& p, const W4Row& w, long c_, float* v, char*
   }
   if (p.rowadd) add8(v, p.rowadd + w.ro_rowadd + c);
   if constexpr (ACT == ACT_GELU_TANH) {
+    // (aux: the bf16 pre-activation kept for the backward, laid out like C -- launch_gemm checks ld_aux == ldc
+    // and an identity C row map -- and read through a fresh laundered argument pointer at its one use, so it
+    // costs the epilogue no live scalar registers; a launch with aux never takes the lean epilogue)
+    if (bf16_t* ax = kernarg_args().aux) {
+      float a[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) a[e] = bfround(v[e]);
+      stbf8(sv ? ax + w.ro_c + c : reinterpret_cast<bf16_t*>(sink), a);
+    }
 #pragma unroll
     for (int e = 0; e < 8; e += 2) {
       const f32x2_t y = gelu_tanh2(bfround2(f32x2_t{v[e], v[e + 1]}));

@@ -361,7 +361,7 @@ int launch_gather_dy(const float* dx, int B, int N, int Spad, int H, bf16_t* dy,
 // over chunks in chunk order.  A lane owns 8 adjacent columns (16-B loads) and keeps 8 rows' loads in flight,
 // adding them in row order; the chunk count is chosen so the grid holds >= 4096 waves where the partial buffer
 // allows it (1152 columns: 144 lanes per row, so 64 chunks left the chip latency-bound at 0.6 TB/s).
-__global__ void __launch_bounds__(64) colsum_partial_kernel(const bf16_t* __restrict__ x, int rows, int cols,
+__global__ void __launch_bounds__(64) colsum_partial_kernel(const bf16_t* __restrict__ x, long ld, int rows, int cols,
                                                             int per, float* __restrict__ partial) {
   const int cg = blockIdx.x * 64 + threadIdx.x;
   if (cg * 8 >= cols) return;
@@ -372,14 +372,14 @@ __global__ void __launch_bounds__(64) colsum_partial_kernel(const bf16_t* __rest
   for (; r + 8 <= r1; r += 8) {
     u16x8_t u[8];
 #pragma unroll
-    for (int j = 0; j < 8; ++j) u[j] = *reinterpret_cast<const u16x8_t*>(xp + (long)(r + j) * cols);
+    for (int j = 0; j < 8; ++j) u[j] = *reinterpret_cast<const u16x8_t*>(xp + (long)(r + j) * ld);
 #pragma unroll
     for (int j = 0; j < 8; ++j)
 #pragma unroll
       for (int e = 0; e < 8; ++e) s[e] += bf2f(u[j][e]);
   }
   for (; r < r1; ++r) {
-    const u16x8_t u = *reinterpret_cast<const u16x8_t*>(xp + (long)r * cols);
+    const u16x8_t u = *reinterpret_cast<const u16x8_t*>(xp + (long)r * ld);
 #pragma unroll
     for (int e = 0; e < 8; ++e) s[e] += bf2f(u[e]);
   }
@@ -420,9 +420,10 @@ __global__ void __launch_bounds__(256) colsum_final_kernel(const float* __restri
   }
 }
 template <typename TO>
-static int colsum_bf16_t(const bf16_t* x, int rows, int cols, TO* out, float* partial, long part_floats,
+static int colsum_bf16_t(const bf16_t* x, long ld, int rows, int cols, TO* out, float* partial, long part_floats,
                          hipStream_t st) {
-  if (cols % 8 || ((uintptr_t)x & 15) || ((uintptr_t)partial & 15)) return set_error("colsum: cols %% 8 / alignment");
+  if (cols % 8 || ld % 8 || ld < cols || ((uintptr_t)x & 15) || ((uintptr_t)partial & 15))
+    return set_error("colsum: cols %% 8 / row stride / alignment");
   if (rows <= 0 || cols <= 0) return 0;
   if (part_floats < cols) return set_error("colsum: partial scratch of %ld floats for %d columns", part_floats, cols);
   const int lanes = cols / 8, blocks_x = (lanes + 63) / 64;
@@ -430,18 +431,22 @@ static int colsum_bf16_t(const bf16_t* x, int rows, int cols, TO* out, float* pa
   chunks = std::max<long>(1, std::min<long>(chunks, part_floats / cols));
   const int per = (int)((rows + chunks - 1) / chunks);
   chunks = (rows + per - 1) / per;
-  hipLaunchKernelGGL(colsum_partial_kernel, dim3((unsigned)blocks_x, (unsigned)chunks), dim3(64), 0, st, x, rows, cols,
+  hipLaunchKernelGGL(colsum_partial_kernel, dim3((unsigned)blocks_x, (unsigned)chunks), dim3(64), 0, st, x, ld, rows, cols,
                      per, partial);
   hipLaunchKernelGGL(colsum_final_kernel<TO>, dim3((cols + 31) / 32), dim3(256), 0, st, partial, cols, (int)chunks, out);
   RET_OK("colsum");
 }
 int launch_colsum_bf16(const bf16_t* x, int rows, int cols, float* out, float* partial, long part_floats,
                        hipStream_t st) {
-  return colsum_bf16_t(x, rows, cols, out, partial, part_floats, st);
+  return colsum_bf16_t(x, cols, rows, cols, out, partial, part_floats, st);
 }
 int launch_colsum_bf16_acc(const bf16_t* x, int rows, int cols, bf16_t* grad, float* partial, long part_floats,
                            hipStream_t st) {
-  return colsum_bf16_t(x, rows, cols, grad, partial, part_floats, st);
+  return colsum_bf16_t(x, cols, rows, cols, grad, partial, part_floats, st);
+}
+int launch_colsum_bf16_acc_ld(const bf16_t* x, long ld, int rows, int cols, bf16_t* grad, float* partial,
+                              long part_floats, hipStream_t st) {
+  return colsum_bf16_t(x, ld, rows, cols, grad, partial, part_floats, st);
 }
 
 // ---------------------------------------------------------------- grad norm + clip + AdamW

@@ -165,6 +165,67 @@ SiglipWs siglip_layout(Bump& bp, const ptk_siglip_config* c, int B) {
   return w;
 }
 
+// The trained tower's workspace: what ptk_siglip_train_fwd keeps for ptk_siglip_bwd, then the backward's scratch.
+// Saved per layer: the residual stream at layer entry (x[l]; x[layers] feeds the post-LN) and after attention
+// (x_mid), q|k|v, the attention output, the flash LSE, the fc1 pre-activation and the GELU output: 2 M (6 D + 2 I)
+// bytes + 4 M heads.  The LN outputs are recomputed into `a`.
+struct SiglipLayerSave {
+  bf16_t *x_mid, *qkv, *o, *pre, *g;
+  float* lse;
+};
+struct SiglipTrainWs {
+  bf16_t* patches;
+  std::vector<bf16_t*> x;            // layers + 1 residual-stream snapshots
+  std::vector<SiglipLayerSave> L;
+  bf16_t *a, *dh, *dtmp, *dI, *dqkv;   // LN output; d(residual stream); dX GEMM outputs [M, D]; dg / dpre [M, I]
+  bf16_t *Qh, *Kh, *Vh, *dOh, *dQh, *dKh, *dVh;   // head-major [B heads][N][64] operands of the flash backward
+  float* delta;
+  bf16_t* wT;                        // the transposed weight of the running dX GEMM
+  bf16_t *TA, *TB;                   // weight_grad's transposed operands (shapes the TN GEMM does not take)
+  float *lnpart, *cpart, *skpart;
+  long lnpart_floats, cpart_floats, sk_floats;
+  void* tail;
+};
+
+SiglipTrainWs siglip_train_layout(Bump& bp, const ptk_siglip_config* c, int B) {
+  const long D = c->hidden, I = c->intermediate, P = c->patch_size, Nn = (c->image_size / P) * (c->image_size / P);
+  const long M = B * Nn, Mp = (M + 63) / 64 * 64, H = c->heads, Kp = (long)c->channels * P * P;
+  SiglipTrainWs w;
+  w.patches = bp.take<bf16_t>(M * Kp);
+  for (int l = 0; l <= c->layers; ++l) w.x.push_back(bp.take<bf16_t>(M * D));
+  for (int l = 0; l < c->layers; ++l) {
+    SiglipLayerSave s;
+    s.x_mid = bp.take<bf16_t>(M * D);
+    s.qkv = bp.take<bf16_t>(M * 3 * D);
+    s.o = bp.take<bf16_t>(M * D);
+    s.pre = bp.take<bf16_t>(M * I);
+    s.g = bp.take<bf16_t>(M * I);
+    s.lse = bp.take<float>(M * H);
+    w.L.push_back(s);
+  }
+  w.a = bp.take<bf16_t>(M * D);
+  w.dh = bp.take<bf16_t>(M * D);
+  w.dtmp = bp.take<bf16_t>(M * D);
+  w.dI = bp.take<bf16_t>(M * I);
+  w.dqkv = bp.take<bf16_t>(M * 3 * D);
+  for (bf16_t** p : {&w.Qh, &w.Kh, &w.Vh, &w.dOh, &w.dQh, &w.dKh, &w.dVh}) *p = bp.take<bf16_t>(M * D);
+  w.delta = bp.take<float>(M * H);
+  w.wT = bp.take<bf16_t>(std::max(3 * D, I) * D);
+  w.TA = bp.take<bf16_t>(std::max(3 * D, I) * Mp);
+  w.TB = bp.take<bf16_t>(std::max(std::max(I, D), Kp) * Mp);
+  w.lnpart_floats = layernorm_bwd_partial_floats((int)M, (int)D);
+  w.lnpart = bp.take<float>(w.lnpart_floats);
+  w.cpart_floats = 256 * std::max(3 * D, I);
+  w.cpart = bp.take<float>(w.cpart_floats);
+  // weight_grad's fp32 scratch: the TN GEMM's stream-K slabs, or 4 K slices of the largest dW
+  w.sk_floats = 4 * std::max(std::max(3 * D, I) * D, D * Kp);
+  w.sk_floats = std::max(w.sk_floats, (long)(p8_tail_scratch_bytes() / sizeof(float)) + 64);
+  w.sk_floats = std::max(w.sk_floats, (long)(tn_slab_bytes() / sizeof(float)));
+  w.skpart = bp.take<float>(w.sk_floats);
+  w.tail = bp.take<char>(p8_tail_scratch_bytes_models());
+  return w;
+}
+
 // ------------------------------------------------------------------ Gemma3
 struct GemmaLayerSave {
   float *x2, *rstd_in, *rstd_ao, *rstd_pre, *rstd_dn, *rstd_q, *rstd_k;
@@ -400,19 +461,32 @@ size_t ptk_siglip_workspace_bytes(const ptk_siglip_config* c, int batch) {
   return bp.off + 256;
 }
 
-int ptk_siglip_fwd(const ptk_siglip_config* c, const ptk_siglip_weights* wt, int B, const void* pixels, void* out,
-                   void* ws, size_t ws_bytes, void* stream) {
-  hipStream_t st = (hipStream_t)stream;
-  if (ws_bytes < ptk_siglip_workspace_bytes(c, B)) return set_error("siglip_fwd: workspace too small");
-  if (c->hidden % c->heads) return set_error("siglip_fwd: hidden %% heads");
+}  // extern "C"
+
+namespace {
+
+// where one forward keeps its activations: the frozen call reuses one buffer of each kind for every layer (the
+// residual GEMMs run in place), the training call gives every layer its own (tw) and keeps the LSE and the fc1
+// pre-activation as well.  The launches are the same either way
+struct SiglipFwdBufs {
+  bf16_t *patches, *a;
+  const SiglipWs* fw = nullptr;
+  const SiglipTrainWs* tw = nullptr;
+  bf16_t* x(int l) const { return tw ? tw->x[l] : fw->h; }
+  bf16_t* x_mid(int l) const { return tw ? tw->L[l].x_mid : fw->h; }
+  bf16_t* qkv(int l) const { return tw ? tw->L[l].qkv : fw->qkv; }
+  bf16_t* o(int l) const { return tw ? tw->L[l].o : fw->o; }
+  bf16_t* g(int l) const { return tw ? tw->L[l].g : fw->mlp; }
+  bf16_t* pre(int l) const { return tw ? tw->L[l].pre : nullptr; }
+  float* lse(int l) const { return tw ? tw->L[l].lse : nullptr; }
+};
+
+int siglip_forward(const ptk_siglip_config* c, const ptk_siglip_weights* wt, int B, const void* pixels, void* out,
+                   const SiglipFwdBufs& w, hipStream_t st) {
+  const bool train = w.tw != nullptr;   // trained weights: never the k-step-tiled copies (they would be stale)
   const int D = c->hidden, I = c->intermediate, P = c->patch_size, Hh = c->heads, hd = D / Hh;
-  const int Nn = (c->image_size / P) * (c->image_size / P), Np = (Nn + 63) / 64 * 64, M = B * Nn;
+  const int Nn = (c->image_size / P) * (c->image_size / P), M = B * Nn;
   const int Kp = c->channels * P * P;
-  if (Kp % 64 || hd % 64) return set_error("siglip_fwd: patch dim %d and head dim %d must be multiples of 64", Kp, hd);
-  Bump bp(ws);
-  SiglipWs w = siglip_layout(bp, c, B);
-  TailScratchScope tail(w.tail, st);
-  CK(tail.status);
   StageScope stage_all("siglip.fwd", st);
   StageSeq sq(st);
   sq.next("siglip.embed");
@@ -420,7 +494,7 @@ int ptk_siglip_fwd(const ptk_siglip_config* c, const ptk_siglip_weights* wt, int
   // K1 patch embed: im2col + GEMM; bf16(conv + bias) + pos -> bf16 residual stream (modeling_siglip.py:175-186)
   CK(launch_im2col((const bf16_t*)pixels, w.patches, B, c->channels, c->image_size, c->image_size, P, st));
   {
-    GemmArgs g = gemm(w.patches, Kp, wt->patch_w, Kp, w.h, D, M, D, Kp);
+    GemmArgs g = gemm(w.patches, Kp, wt->patch_w, Kp, w.x(0), D, M, D, Kp);
     g.bias = wt->patch_b;
     g.bf16_linear = 1;
     g.rowadd = wt->pos; g.rowadd_period = Nn; g.ld_rowadd = D;
@@ -429,15 +503,15 @@ int ptk_siglip_fwd(const ptk_siglip_config* c, const ptk_siglip_weights* wt, int
   for (int l = 0; l < c->layers; ++l) {
     const ptk_siglip_layer& L = wt->layers[l];
     sq.next("siglip.attn");
-    CK(launch_layernorm_bf16(w.h, L.ln1_w, L.ln1_b, w.a, M, D, c->eps, st));
+    CK(launch_layernorm_bf16(w.x(l), L.ln1_w, L.ln1_b, w.a, M, D, c->eps, st));
     {  // fused q|k|v projection
-      GemmArgs g = gemm(w.a, D, L.wqkv, D, w.qkv, 3 * D, M, 3 * D, D, L.wqkv_kt);
+      GemmArgs g = gemm(w.a, D, L.wqkv, D, w.qkv(l), 3 * D, M, 3 * D, D, train ? nullptr : L.wqkv_kt);
       g.bias = L.bqkv;
       CK(launch_gemm(g, ACT_NONE, OUT_BF16, 1, st));
     }
     {  // softmax(Q K^T / sqrt(hd)) V per (b, head), flash (no score matrix in HBM)
       FlashArgs fa;
-      fa.Q = w.qkv; fa.K = w.qkv + D; fa.V = w.qkv + 2 * D; fa.O = w.o;
+      fa.Q = w.qkv(l); fa.K = w.qkv(l) + D; fa.V = w.qkv(l) + 2 * D; fa.O = w.o(l); fa.lse = w.lse(l);
       fa.rows = Nn; fa.nkeys = Nn; fa.D = hd;
       fa.ldq = fa.ldk = 3 * D; fa.ldo = D;
       fa.zin = Hh; fa.zdiv = Hh;
@@ -448,26 +522,179 @@ int ptk_siglip_fwd(const ptk_siglip_config* c, const ptk_siglip_weights* wt, int
       CK(launch_attn_fwd(fa, B * Hh, st));
     }
     {  // h = bf16(h + bf16(out_proj + bias))   (modeling_siglip.py:343-346, bf16 module)
-      GemmArgs g = gemm(w.o, D, L.wo, D, w.h, D, M, D, D, L.wo_kt);
-      g.bias = L.bo; g.bf16_linear = 1; g.resid16 = w.h; g.ld_resid16 = D;
+      GemmArgs g = gemm(w.o(l), D, L.wo, D, w.x_mid(l), D, M, D, D, train ? nullptr : L.wo_kt);
+      g.bias = L.bo; g.bf16_linear = 1; g.resid16 = w.x(l); g.ld_resid16 = D;
       CK(launch_gemm(g, ACT_NONE, OUT_BF16, 1, st));
     }
     sq.next("siglip.mlp");
-    CK(launch_layernorm_bf16(w.h, L.ln2_w, L.ln2_b, w.a, M, D, c->eps, st));
+    CK(launch_layernorm_bf16(w.x_mid(l), L.ln2_w, L.ln2_b, w.a, M, D, c->eps, st));
     {
-      GemmArgs g = gemm(w.a, D, L.w1, D, w.mlp, I, M, I, D, L.w1_kt);
+      GemmArgs g = gemm(w.a, D, L.w1, D, w.g(l), I, M, I, D, train ? nullptr : L.w1_kt);
       g.bias = L.b1;
+      g.aux = w.pre(l); g.ld_aux = I;   // training: the bf16 pre-activation beside the activation
       CK(launch_gemm(g, ACT_GELU_TANH, OUT_BF16, 1, st));
     }
     {  // h = bf16(h + bf16(fc2 + bias))
-      GemmArgs g = gemm(w.mlp, I, L.w2, I, w.h, D, M, D, I, L.w2_kt);
-      g.bias = L.b2; g.bf16_linear = 1; g.resid16 = w.h; g.ld_resid16 = D;
+      GemmArgs g = gemm(w.g(l), I, L.w2, I, w.x(l + 1), D, M, D, I, train ? nullptr : L.w2_kt);
+      g.bias = L.b2; g.bf16_linear = 1; g.resid16 = w.x_mid(l); g.ld_resid16 = D;
       CK(launch_gemm(g, ACT_NONE, OUT_BF16, 1, st));
     }
   }
   sq.next("siglip.post_norm");
-  CK(launch_layernorm_bf16(w.h, wt->post_w, wt->post_b, (bf16_t*)out, M, D, c->eps, st));
+  CK(launch_layernorm_bf16(w.x(c->layers), wt->post_w, wt->post_b, (bf16_t*)out, M, D, c->eps, st));
   return 0;
+}
+
+// the shapes the trained tower takes, checked before any launch
+int siglip_train_check(const char* who, const ptk_siglip_config* c, int B, const void* ws, size_t ws_bytes) {
+  if (!c || B <= 0) return set_error("%s: null config or batch %d", who, B);
+  if (c->heads <= 0 || c->hidden % c->heads) return set_error("%s: hidden %% heads", who);
+  const int P = c->patch_size, Nn = (c->image_size / P) * (c->image_size / P), hd = c->hidden / c->heads;
+  if (Nn % 64)
+    return set_error("%s: num_patches %d must be a multiple of 64 (the flash attention backward takes whole 64-row "
+                     "blocks; padding is not implemented)", who, Nn);
+  if (hd != 64) return set_error("%s: head_dim %d must be 64 (the SigLIP flash attention backward)", who, hd);
+  if ((c->channels * P * P) % 64 || c->intermediate % 64)
+    return set_error("%s: patch dim %d and intermediate %d must be multiples of 64", who, c->channels * P * P,
+                     c->intermediate);
+  if (!ws || ws_bytes < ptk_siglip_train_workspace_bytes(c, B))
+    return set_error("%s: workspace too small (%zu bytes, %zu needed)", who, ws_bytes,
+                     ptk_siglip_train_workspace_bytes(c, B));
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ptk_siglip_fwd(const ptk_siglip_config* c, const ptk_siglip_weights* wt, int B, const void* pixels, void* out,
+                   void* ws, size_t ws_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (ws_bytes < ptk_siglip_workspace_bytes(c, B)) return set_error("siglip_fwd: workspace too small");
+  if (c->hidden % c->heads) return set_error("siglip_fwd: hidden %% heads");
+  const int P = c->patch_size, hd = c->hidden / c->heads, Kp = c->channels * P * P;
+  if (Kp % 64 || hd % 64) return set_error("siglip_fwd: patch dim %d and head dim %d must be multiples of 64", Kp, hd);
+  Bump bp(ws);
+  SiglipWs w = siglip_layout(bp, c, B);
+  TailScratchScope tail(w.tail, st);
+  CK(tail.status);
+  SiglipFwdBufs b;
+  b.patches = w.patches; b.a = w.a; b.fw = &w;
+  return siglip_forward(c, wt, B, pixels, out, b, st);
+}
+
+size_t ptk_siglip_train_workspace_bytes(const ptk_siglip_config* c, int batch) {
+  if (!c || batch <= 0) return 0;
+  Bump bp(nullptr);
+  siglip_train_layout(bp, c, batch);
+  return bp.off + 256;
+}
+
+int ptk_siglip_train_fwd(const ptk_siglip_config* c, const ptk_siglip_weights* wt, int B, const void* pixels,
+                         void* out, void* ws, size_t ws_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  CK(siglip_train_check("siglip_train_fwd", c, B, ws, ws_bytes));
+  if (!wt || !pixels || !out) return set_error("siglip_train_fwd: null argument");
+  Bump bp(ws);
+  SiglipTrainWs w = siglip_train_layout(bp, c, B);
+  TailScratchScope tail(w.tail, st);
+  CK(tail.status);
+  SiglipFwdBufs b;
+  b.patches = w.patches; b.a = w.a; b.tw = &w;
+  return siglip_forward(c, wt, B, pixels, out, b, st);
+}
+
+// The tower's backward from the activations ptk_siglip_train_fwd left in ws.  dh walks the residual stream's grad
+// down the layers; each sub-block: bias grad (column sum of the branch's output grad, which is dh itself), weight
+// grad (TN GEMM on the token-major operands), dX GEMM against the weight transposed into wT, and the LayerNorm
+// backward with the residual add folded in (dh = bf16(dh + dLN)).
+int ptk_siglip_bwd(const ptk_siglip_config* c, const ptk_siglip_weights* wt, int B, const void* d_out,
+                   const ptk_siglip_grads* gr, void* ws, size_t ws_bytes, void* stream) {
+  hipStream_t st = (hipStream_t)stream;
+  CK(siglip_train_check("siglip_bwd", c, B, ws, ws_bytes));
+  if (!wt || !d_out || !gr || !gr->layers) return set_error("siglip_bwd: null argument");
+  const int D = c->hidden, I = c->intermediate, P = c->patch_size, Hh = c->heads, hd = D / Hh;
+  const int Nn = (c->image_size / P) * (c->image_size / P), M = B * Nn, Kp = c->channels * P * P, nl = c->layers;
+  Bump bp(ws);
+  SiglipTrainWs w = siglip_train_layout(bp, c, B);
+  TailScratchScope tail(w.tail, st);
+  CK(tail.status);
+  const RowMap ident{0, 0, 0, 0};
+  auto bias_grad = [&](const bf16_t* dy, int cols, void* grad) {
+    return launch_colsum_bf16_acc(dy, M, cols, (bf16_t*)grad, w.cpart, w.cpart_floats, st);
+  };
+  auto wgrad = [&](const bf16_t* dy, int Ny, const bf16_t* x, int Nx, void* grad) {
+    return weight_grad(dy, Ny, ident, Ny, x, Nx, ident, Nx, M, w.TA, w.TB, grad, w.skpart, w.sk_floats, st);
+  };
+  // dx [M, Nw_in] = bf16(dy [M, Nw_out] . W), W [Nw_out, Nw_in] row-major: W^T is the GEMM's K-contiguous B
+  auto dx_gemm = [&](const bf16_t* dy, const void* W, int n_out, int n_in, bf16_t* dx) {
+    CK(launch_transpose((const bf16_t*)W, n_in, 0, 0, 1, w.wT, n_out, 0, 0, 1, n_out, n_in, n_out, st));
+    return launch_gemm(gemm(dy, n_out, w.wT, n_out, dx, n_in, M, n_in, n_out), ACT_NONE, OUT_BF16, 1, st);
+  };
+  StageScope stage_all("siglip.bwd", st);
+  StageSeq sq(st);
+  sq.next("siglip.bwd.post_norm");
+  CK(launch_layernorm_bwd_bf16(w.x[nl], wt->post_w, (const bf16_t*)d_out, nullptr, w.dh, M, D, c->eps,
+                               (bf16_t*)gr->post_w, (bf16_t*)gr->post_b, w.lnpart, w.lnpart_floats, st));
+  for (int l = nl - 1; l >= 0; --l) {
+    const ptk_siglip_layer& L = wt->layers[l];
+    const ptk_siglip_layer_grads& G = gr->layers[l];
+    const SiglipLayerSave& sv = w.L[l];
+    sq.next("siglip.bwd.mlp");
+    // fc2: x[l + 1] = bf16(x_mid + bf16(g W2^T + b2))
+    CK(bias_grad(w.dh, D, G.b2));
+    CK(wgrad(w.dh, D, sv.g, I, G.w2));
+    CK(dx_gemm(w.dh, L.w2, D, I, w.dI));                                   // dg
+    CK(launch_gelu_tanh_bwd_bf16(w.dI, sv.pre, w.dI, M, I, st));           // dpre, in place
+    // fc1 over a2 = LN2(x_mid), recomputed
+    CK(bias_grad(w.dI, I, G.b1));
+    CK(launch_layernorm_bf16(sv.x_mid, L.ln2_w, L.ln2_b, w.a, M, D, c->eps, st));
+    CK(wgrad(w.dI, I, w.a, D, G.w1));
+    CK(dx_gemm(w.dI, L.w1, I, D, w.dtmp));                                 // da2
+    CK(launch_layernorm_bwd_bf16(sv.x_mid, L.ln2_w, w.dtmp, w.dh, w.dh, M, D, c->eps, (bf16_t*)G.ln2_w,
+                                 (bf16_t*)G.ln2_b, w.lnpart, w.lnpart_floats, st));
+    sq.next("siglip.bwd.attn");
+    // out_proj: x_mid = bf16(x[l] + bf16(o Wo^T + bo))
+    CK(bias_grad(w.dh, D, G.bo));
+    CK(wgrad(w.dh, D, sv.o, D, G.wo));
+    CK(dx_gemm(w.dh, L.wo, D, D, w.dtmp));                                 // do, token-major
+    {  // non-causal flash attention backward on head-major copies ([B heads][N][64])
+      StageScope sf("siglip.bwd.flash", st);
+      CK(launch_heads_split(sv.qkv, 3 * D, w.Qh, B, Nn, Hh, hd, st));
+      CK(launch_heads_split(sv.qkv + D, 3 * D, w.Kh, B, Nn, Hh, hd, st));
+      CK(launch_heads_split(sv.qkv + 2 * D, 3 * D, w.Vh, B, Nn, Hh, hd, st));
+      CK(launch_heads_split(w.dtmp, D, w.dOh, B, Nn, Hh, hd, st));
+      FlashBwdArgs fb;
+      fb.Q = w.Qh; fb.K = w.Kh; fb.V = w.Vh; fb.O = sv.o; fb.dO = w.dOh; fb.lse = sv.lse; fb.delta = w.delta;
+      fb.dQ = w.dQh; fb.dK = w.dKh; fb.dV = w.dVh;
+      fb.rows = Nn; fb.nkeys = Nn; fb.D = hd;
+      fb.zin = Hh; fb.zdiv = Hh;
+      fb.ldo = D; fb.sO0 = (long)Nn * D; fb.sO1 = hd;
+      fb.scale = 1.0f / sqrtf((float)hd);
+      CK(launch_attn_bwd(fb, B * Hh, st));
+      CK(launch_heads_merge(w.dQh, w.dqkv, 3 * D, B, Nn, Hh, hd, st));
+      CK(launch_heads_merge(w.dKh, w.dqkv + D, 3 * D, B, Nn, Hh, hd, st));
+      CK(launch_heads_merge(w.dVh, w.dqkv + 2 * D, 3 * D, B, Nn, Hh, hd, st));
+    }
+    // q|k|v over a1 = LN1(x[l]), recomputed; the fused rows make da1 one GEMM with K = 3 D.  The bias grads of
+    // the q and v thirds are column sums of dqkv's column blocks.  The key third's gradient is exactly zero for
+    // every input -- a key bias adds q . b_k to each score of a query's row, which softmax does not see: the
+    // column sum of dK is sum_q (sum_k dS[q, k]) Q[q] and the rows of dS sum to zero -- so nothing is added to it;
+    // summing dK would add only the rounding residue of those row sums (the flash backward takes delta =
+    // rowsum(dO . O) from the bf16-rounded O)
+    CK(launch_colsum_bf16_acc_ld(w.dqkv, 3 * D, M, D, (bf16_t*)G.bqkv, w.cpart, w.cpart_floats, st));
+    CK(launch_colsum_bf16_acc_ld(w.dqkv + 2 * D, 3 * D, M, D, (bf16_t*)G.bqkv + 2 * D, w.cpart, w.cpart_floats, st));
+    CK(launch_layernorm_bf16(w.x[l], L.ln1_w, L.ln1_b, w.a, M, D, c->eps, st));
+    CK(wgrad(w.dqkv, 3 * D, w.a, D, G.wqkv));
+    CK(dx_gemm(w.dqkv, L.wqkv, 3 * D, D, w.dtmp));                         // da1
+    CK(launch_layernorm_bwd_bf16(w.x[l], L.ln1_w, w.dtmp, w.dh, w.dh, M, D, c->eps, (bf16_t*)G.ln1_w,
+                                 (bf16_t*)G.ln1_b, w.lnpart, w.lnpart_floats, st));
+  }
+  // embeddings: x[0] = bf16(bf16(patches Wp^T + bp) + pos[n])
+  sq.next("siglip.bwd.embed");
+  CK(launch_pos_grad_bf16(w.dh, B, Nn, D, (bf16_t*)gr->pos, st));
+  CK(bias_grad(w.dh, D, gr->patch_b));
+  return wgrad(w.dh, D, w.patches, Kp, gr->patch_w);
 }
 
 size_t ptk_gemma3_workspace_bytes(const ptk_gemma3_config* c, int batch, int text_len, int seq_pad) {

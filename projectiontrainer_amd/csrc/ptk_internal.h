@@ -433,6 +433,9 @@ int launch_colsum_bf16(const bf16_t* x, int rows, int cols, float* out, float* p
 // the same column sums accumulated into a bf16 .grad: grad[c] = bf16(grad[c] + bf16(sum)) in the last level
 int launch_colsum_bf16_acc(const bf16_t* x, int rows, int cols, bf16_t* grad, float* partial, long part_floats,
                            hipStream_t st);
+// the same over `cols` columns of rows `ld` elements apart (a column block of a wider matrix; ld % 8 == 0)
+int launch_colsum_bf16_acc_ld(const bf16_t* x, long ld, int rows, int cols, bf16_t* grad, float* partial,
+                              long part_floats, hipStream_t st);
 int launch_sumsq_partial(const float* x, long n, float* partial, int nparts, hipStream_t st);
 int launch_clip_adamw(float* p, const float* g, float* m, float* v, long n, const float* partial,
                       int nparts, float grad_scale, float max_norm, float lr, float b1, float b2,
@@ -527,6 +530,23 @@ int launch_scale_sumsq_bf16(bf16_t* g, long n, float scale, float* partial, floa
 int launch_adamw_bf16(bf16_t* p, bf16_t* g, bf16_t* m, bf16_t* v, long n, const float* sumsq, float max_norm,
                       double lr, double b1, double b2, double eps, double wd, int step, float* norm_out,
                       hipStream_t st);
+
+// ---- SigLIP tower backward (siglip_bwd.hip) ----
+// dx = bf16(dacc + d/dx LayerNorm(x; w) applied to dy) over bf16 rows (dacc may be null or alias dx; mean and rstd
+// recomputed from x); with dw / db (both or neither) also dw = bf16(dw + bf16(colsum(dy xhat))), db = bf16(db +
+// bf16(colsum(dy))) from fp32 per-workgroup partials folded in a fixed order; partial >=
+// layernorm_bwd_partial_floats(rows, cols) floats.  cols % 8 == 0, cols <= 2048
+long layernorm_bwd_partial_floats(int rows, int cols);
+int launch_layernorm_bwd_bf16(const bf16_t* x, const float* w, const bf16_t* dy, const bf16_t* dacc, bf16_t* dx,
+                              int rows, int cols, float eps, bf16_t* dw, bf16_t* db, float* partial,
+                              long part_floats, hipStream_t st);
+// dpre = bf16(dg * gelu_tanh'(pre)) over packed bf16 [rows][cols] (dpre may alias dg)
+int launch_gelu_tanh_bwd_bf16(const bf16_t* dg, const bf16_t* pre, bf16_t* dpre, long rows, int cols, hipStream_t st);
+// dpos[n][:] = bf16(dpos[n][:] + bf16(sum_b dh0[b N + n][:])), b in index order
+int launch_pos_grad_bf16(const bf16_t* dh0, int B, int N, int D, bf16_t* dpos, hipStream_t st);
+// heads [B][H][N][hd] <-> columns [h hd, (h + 1) hd) of the token-major rows tok[(b N + n) ld]
+int launch_heads_split(const bf16_t* tok, long ld, bf16_t* heads, int B, int N, int H, int hd, hipStream_t st);
+int launch_heads_merge(const bf16_t* heads, bf16_t* tok, long ld, int B, int N, int H, int hd, hipStream_t st);
 
 }  // namespace ptk
 #include "../../include/ptk.h"

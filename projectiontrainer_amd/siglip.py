@@ -1,4 +1,5 @@
-"""Frozen SigLIP vision tower on libptk (`ptk_siglip_fwd`).
+"""SigLIP vision tower on libptk: the frozen forward (`ptk_siglip_fwd`) and, for a trained tower, the training
+forward and the backward (`ptk_siglip_train_fwd` / `ptk_siglip_bwd`, driven through a `stage2.SiglipTrainState`).
 
 Replaces the reference's `vision_tower(pixel_values=...).last_hidden_state`
 call (Stage1/projector_trainer.py:158-171), i.e. HF `SiglipVisionModel`
@@ -85,14 +86,16 @@ class SiglipVisionTower:
         self._ws = None
         return self
 
-    def _build_c(self):
+    def _build_c(self, ktiled=True):
+        """ktiled=False (a trained tower, SiglipTrainState): no k-step-tiled weight copies, which are copies of
+        frozen weights and would go stale; every GEMM reads the row-major weights (bit-identical)."""
         c = self.cfg
         self.c_cfg = L.SiglipConfigC(c.image_size, c.patch_size, c.num_channels, c.hidden_size,
                                      c.num_attention_heads, c.intermediate_size, c.num_hidden_layers,
                                      c.layer_norm_eps)
         arr = (L.SiglipLayerC * len(self.layers))()
         for lay in self.layers:   # the tower is frozen in both stages: k-step-tiled copies of its GEMM weights
-            lay["kt"] = {k: K.frozen_kstep_tiles(lay[k]) for k in ("wqkv", "wo", "w1", "w2")}
+            lay["kt"] = {k: K.frozen_kstep_tiles(lay[k]) if ktiled else None for k in ("wqkv", "wo", "w1", "w2")}
         for i, lay in enumerate(self.layers):
             arr[i] = L.SiglipLayerC(*[lay[k].data_ptr() for k in ("wqkv", "bqkv", "wo", "bo", "w1", "b1", "w2", "b2",
                                                                    "ln1_w", "ln1_b", "ln2_w", "ln2_b")],
@@ -115,6 +118,24 @@ class SiglipVisionTower:
         L.check(L.lib().ptk_siglip_fwd(self.c_cfg, self.c_w, B, pixels_bf16.data_ptr(), out.data_ptr(),
                                        ws.data_ptr(), ws.numel(), L.stream_ptr(self.device)), "ptk_siglip_fwd")
         return out
+
+    def forward_train_into(self, pixels_bf16, out, state):
+        """forward_into (bit-identical `out`) that keeps the activations `backward` reads in the state's workspace
+        (ptk_siglip_train_fwd); state: the stage2.SiglipTrainState this tower's tensors are views of."""
+        B = pixels_bf16.shape[0]
+        ws = state.workspace(B)
+        L.check(L.lib().ptk_siglip_train_fwd(self.c_cfg, self.c_w, B, pixels_bf16.data_ptr(), out.data_ptr(),
+                                             ws.data_ptr(), ws.numel(), L.stream_ptr(self.device)),
+                "ptk_siglip_train_fwd")
+        return out
+
+    def backward(self, d_out, state):
+        """d_out bf16 [B*N, D], the grad of the last forward_train_into's `out`: every parameter grad accumulated
+        into state.grad (ptk_siglip_bwd).  d(pixels) is not computed."""
+        B = d_out.shape[0] // self.cfg.num_patches
+        ws = state.workspace(B)
+        L.check(L.lib().ptk_siglip_bwd(self.c_cfg, self.c_w, B, d_out.data_ptr(), state.c_grads, ws.data_ptr(),
+                                       ws.numel(), L.stream_ptr(self.device)), "ptk_siglip_bwd")
 
     def __call__(self, pixel_values):
         """HF-style: pixel_values [B,C,H,W] (any float dtype) -> last_hidden_state bf16 [B,N,D]."""

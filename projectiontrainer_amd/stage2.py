@@ -1,10 +1,11 @@
-"""Stage 2 (VQA fine-tune) on MI355X: the Gemma3 step with the LLM and / or the projector trained.
+"""Stage 2 (VQA fine-tune) on MI355X: the Gemma3 step with the LLM, the projector and / or the vision tower trained.
 
-Three of the reference's Stage-2 modes run here (the vision tower is frozen in all; QLoRA is not supported):
+Three of the reference's Stage-2 modes run here (QLoRA is not supported):
   A  --unfreeze_llm                                   (BASELINE cfg4; the default)   AdamW over the LLM
   B  --unfreeze_llm --unfreeze_projection_layer                                      AdamW over LLM + projector
   C  --unfreeze_projection_layer (LLM frozen)                                        AdamW over the projector
-Mode A is described first; the trainable projector of B and C follows below.
+each with the vision tower frozen (the default) or trained as well (train_vision=True, which is also valid alone).
+Mode A is described first; the trainable projector of B and C and the trainable tower follow below.
 
 The body of `with self.accelerator.accumulate(...)` in VQATrainerStage2.train
 (Stage2/trainer.py:299-444) with the cfg4 flags (`--unfreeze_llm`; projector
@@ -45,6 +46,26 @@ parameters, next to the LLM's 2 GB reduce-scatter), scaled by 1 / world before t
 takes the same deterministic step, so the replicas stay bit-identical without a parameter exchange.
 Mode C builds no Gemma3TrainState: the LLM keeps the k-step-tiled frozen weights it was built with and runs
 ptk_gemma3_loss_fwd_bwd (loss and dX only, label_offset = the question length).
+
+Trainable vision tower (train_vision=True; the reference's --unfreeze_vision_encoder / first-epoch fine-tune,
+Stage2/trainer.py:214-237,267-289, whose two flags exclude each other in its run script, so the tower never
+trains there and no recorded step exists to match: the yardstick is torch autograd through
+oracle.stage1_ref.siglip_vision_forward).  The reference loads the tower in bf16 under --mixed_precision bf16
+(train_vqa_stage2.py:141-153): `SiglipTrainState` holds every tower parameter in one flat bf16 store (grads and
+two moments in three more), rebinding the tower's tensors.  Per micro-batch:
+  SigLIP fwd keeping activations                           ptk_siglip_train_fwd (bit-identical to ptk_siglip_fwd)
+  ... projector fwd, Gemma3 fwd / loss / bwd as above ...
+  dy = bf16(dx[vision rows]), patch 0's row zero           ptk_gather_vision_grad
+  [db2, dW2,] dA, [db1, dW1,] d(vis) = bf16(dA W1)         ptk_projector_input_grad (one dA for both uses; the four
+                                                           grads only when the projector is trained)
+  every tower grad, accumulated bf16(grad + bf16(G))       ptk_siglip_bwd; d(vis) is d(last_hidden_state), its
+                                                           patch-0 rows zero ([:, 1:] drops that patch)
+With train_vision=False none of this runs and nothing the engine computes changes.  optimizer_step clips the tower
+on its own norm and applies ptk_adamw_bf16 with the shared LR / step count; the store is replicated like the
+projector's (one all-reduce of ~0.6 GB of bf16 grads for L/16, scaled by 1 / world before the sum of squares, the
+same deterministic step on every rank; its cost next to the LLM's ZeRO-1 exchange is unmeasured).
+set_vision_trainable(False) freezes the tower again (frozen forward, no tower backward, no tower step) while
+keeping its store, moments and the step count: the hook for a first-epoch-only schedule.
 """
 from __future__ import annotations
 
@@ -230,10 +251,131 @@ class ProjectorTrainState:
         return {k: self.view(k, self.grad if grads else None) for k in PROJ_KEYS}
 
 
+SIGLIP_MATS = ("wqkv", "wo", "w1", "w2")
+SIGLIP_SMALL = ("bqkv", "bo", "b1", "b2", "ln1_w", "ln1_b", "ln2_w", "ln2_b")
+SIGLIP_GRAD_KEYS = ("wqkv", "bqkv", "wo", "bo", "w1", "b1", "w2", "b2", "ln1_w", "ln1_b", "ln2_w", "ln2_b")
+SIGLIP_HF = {"wo": "self_attn.out_proj.weight", "bo": "self_attn.out_proj.bias", "w1": "mlp.fc1.weight",
+             "b1": "mlp.fc1.bias", "w2": "mlp.fc2.weight", "b2": "mlp.fc2.bias", "ln1_w": "layer_norm1.weight",
+             "ln1_b": "layer_norm1.bias", "ln2_w": "layer_norm2.weight", "ln2_b": "layer_norm2.bias"}
+
+
+class SiglipTrainState:
+    """Flat bf16 parameter / grad / moment store of a trained SigLIP tower (rebinds the tower's tensors).
+
+    Under `--mixed_precision bf16` the reference loads the vision tower in bf16 (train_vqa_stage2.py:141-153), so its
+    parameters, grads and AdamW moments are bf16 tensors: every parameter lives in ONE flat bf16 buffer in the
+    kernel layouts (q|k|v rows fused, the conv weight flattened (c, ky, kx)), the matrices first, then the
+    positions, biases and LayerNorm parameters in one contiguous region.  The tower's GEMM weights become views
+    of the store; its fp32 positions / biases / LN parameters, which the forward kernels read, become views of one
+    fp32 mirror of that region, refreshed after each optimizer step (as ProjectorTrainState.refresh does).  The
+    k-step-tiled weight copies are dropped: they are copies of frozen weights.  The grads live in a second
+    buffer of the same layout (ptk_siglip_bwd accumulates into it), the moments in two more."""
+
+    ALIGN = 64   # elements
+
+    def __init__(self, tower: SiglipVisionTower):
+        self.tower = tower
+        dev = tower.device
+        nl = len(tower.layers)
+        segs = [("patch_w", tuple(tower.patch_w.shape))]
+        for i, lay in enumerate(tower.layers):
+            segs += [(f"{i}.{k}", tuple(lay[k].shape)) for k in SIGLIP_MATS]
+        small = [(k, tuple(getattr(tower, k).shape)) for k in ("patch_b", "pos", "post_w", "post_b")]
+        for i, lay in enumerate(tower.layers):
+            small += [(f"{i}.{k}", tuple(lay[k].shape)) for k in SIGLIP_SMALL]
+        off, self.offsets = 0, {}
+        for j, (name, shape) in enumerate(segs + small):
+            if j == len(segs):
+                self.small_lo = off
+            self.offsets[name] = (off, shape)
+            off += (math.prod(shape) + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+        self.small_hi = self.numel = off
+        bf = torch.bfloat16
+        self.flat = torch.zeros(off, dtype=bf, device=dev)
+        self.grad = torch.zeros(off, dtype=bf, device=dev)
+        self.exp_avg = torch.zeros(off, dtype=bf, device=dev)
+        self.exp_avg_sq = torch.zeros(off, dtype=bf, device=dev)
+        self.sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.small32 = torch.zeros(self.small_hi - self.small_lo, dtype=torch.float32, device=dev)
+        # the current weights in (the fp32 ones rounded to bf16, as the reference's bf16-loaded tower holds them),
+        # then the tower rebound onto views of the store / of the fp32 mirror
+        for name, _ in segs + small:
+            self.view(name).copy_(self._tower_tensor(name))
+        s32 = lambda name: self.small32[self.offsets[name][0] - self.small_lo:][:math.prod(self.offsets[name][1])] \
+            .view(self.offsets[name][1])
+        tower.patch_w = self.view("patch_w")
+        for k in ("patch_b", "pos", "post_w", "post_b"):
+            setattr(tower, k, s32(k))
+        for i, lay in enumerate(tower.layers):
+            for k in SIGLIP_MATS:
+                lay[k] = self.view(f"{i}.{k}")
+            for k in SIGLIP_SMALL:
+                lay[k] = s32(f"{i}.{k}")
+        self.refresh()
+        tower._build_c(ktiled=False)
+        arr = (L.SiglipLayerGradsC * nl)()
+        for i in range(nl):
+            arr[i] = L.SiglipLayerGradsC(*[self.grad_view(f"{i}.{k}").data_ptr() for k in SIGLIP_GRAD_KEYS])
+        self._c_layer_grads = arr
+        self.c_grads = L.SiglipGradsC(*[self.grad_view(k).data_ptr() for k in ("patch_w", "patch_b", "pos", "post_w",
+                                                                                 "post_b")], arr)
+        self._ws = None
+
+    def _tower_tensor(self, name):
+        if "." in name:
+            i, k = name.split(".")
+            return self.tower.layers[int(i)][k]
+        return getattr(self.tower, name)
+
+    def view(self, name, buf=None):
+        off, shape = self.offsets[name]
+        return (self.flat if buf is None else buf)[off:off + math.prod(shape)].view(shape)
+
+    def grad_view(self, name):
+        return self.view(name, self.grad)
+
+    def refresh(self):
+        """The fp32 copies the forward kernels read (positions, biases, LN parameters)."""
+        self.small32.copy_(self.flat[self.small_lo:self.small_hi])
+
+    def workspace(self, batch):
+        """Saved activations + backward scratch of ptk_siglip_train_fwd / ptk_siglip_bwd at this batch."""
+        n = L.lib().ptk_siglip_train_workspace_bytes(self.tower.c_cfg, batch)
+        if self._ws is None or self._ws.numel() < n:
+            self._ws = None
+            self._ws = torch.empty(n, dtype=torch.uint8, device=self.tower.device)
+        return self._ws
+
+    def zero_grad(self):
+        self.grad.zero_()
+
+    def state_dict_hf(self, grads=False):
+        """HF SiglipVisionModel names (`vision_model.*`), bf16 tensors on the device: q|k|v split again, the conv
+        weight as [D, C, P, P]."""
+        c = self.tower.cfg
+        v = self.grad_view if grads else self.view
+        D, p = c.hidden_size, "vision_model."
+        sd = {p + "embeddings.patch_embedding.weight": v("patch_w").view(D, c.num_channels, c.patch_size,
+                                                                          c.patch_size),
+              p + "embeddings.patch_embedding.bias": v("patch_b"),
+              p + "embeddings.position_embedding.weight": v("pos"),
+              p + "post_layernorm.weight": v("post_w"), p + "post_layernorm.bias": v("post_b")}
+        for i in range(len(self.tower.layers)):
+            q = f"{p}encoder.layers.{i}."
+            wqkv, bqkv = v(f"{i}.wqkv"), v(f"{i}.bqkv")
+            for j, n in enumerate("qkv"):
+                sd[q + f"self_attn.{n}_proj.weight"] = wqkv[j * D:(j + 1) * D]
+                sd[q + f"self_attn.{n}_proj.bias"] = bqkv[j * D:(j + 1) * D]
+            for k, hf in SIGLIP_HF.items():
+                sd[q + hf] = v(f"{i}.{k}")
+        return sd
+
+
 class Stage2Engine:
     """One VQATrainerStage2 micro-batch (forward_backward) and optimizer step (optimizer_step).
 
-    train_llm / train_projector select the reference's Stage-2 modes (the vision tower is frozen in all):
+    train_llm / train_projector select the reference's Stage-2 modes; train_vision=True trains the SigLIP tower
+    as well (with any of them, or alone):
       A  train_llm=True,  train_projector=False   ptk_gemma3_train_fwd_bwd; AdamW over the LLM (the default)
       B  train_llm=True,  train_projector=True    the same, then ptk_projector_bwd_bf16; AdamW over both
       C  train_llm=False, train_projector=True    ptk_gemma3_loss_fwd_bwd (dX only, the LLM as it was built --
@@ -243,11 +385,14 @@ class Stage2Engine:
     def __init__(self, vision: SiglipVisionTower, llm: Gemma3CausalLM, projector: MLPProjector, *,
                  learning_rate=1e-4, weight_decay=0.01, gradient_accumulation_steps=1, max_grad_norm=1.0,
                  warmup_steps=0, total_steps=1, betas=(0.9, 0.999), eps=1e-8, world_size=1, rank=0,
-                 process_group=None, pad_token_id=None, zero1=None, train_llm=True, train_projector=False):
-        if not train_llm and not train_projector:
-            raise ValueError("No trainable parameters found. Stage2Engine needs train_llm or train_projector")
+                 process_group=None, pad_token_id=None, zero1=None, train_llm=True, train_projector=False,
+                 train_vision=False):
+        if not train_llm and not train_projector and not train_vision:
+            raise ValueError("No trainable parameters found. Stage2Engine needs train_llm, train_projector or "
+                             "train_vision")
         self.vision, self.llm, self.proj = vision, llm, projector
         self.train_llm, self.train_projector = bool(train_llm), bool(train_projector)
+        self.train_vision = bool(train_vision)
         self.device = vision.device
         self.lr0, self.wd, self.gas, self.max_norm = learning_rate, weight_decay, gradient_accumulation_steps, max_grad_norm
         self.warmup, self.total, self.betas, self.eps = warmup_steps, total_steps, betas, eps
@@ -273,6 +418,12 @@ class Stage2Engine:
         # the LLM's 1 B: its grads are all-reduced whole and every rank takes the same AdamW step)
         self.pstate = ProjectorTrainState(projector, self.device) if self.train_projector else None
         self.proj_grad_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
+        # a trained vision tower: its own bf16 store, replicated like the projector's (one all-reduce of its grads,
+        # the same deterministic step on every rank).  set_vision_trainable(False) freezes it again without
+        # dropping the store, the moments or the step count (a first-epoch-only schedule)
+        self.vstate = SiglipTrainState(vision) if self.train_vision else None
+        self.vision_trainable = self.train_vision
+        self.vision_grad_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._partial = torch.empty(L.lib().ptk_bf16_sumsq_partial_floats(), dtype=torch.float32, device=self.device)
         self.sumsq = torch.zeros(1, dtype=torch.float32, device=self.device)
         self.grad_norm = torch.zeros(1, dtype=torch.float32, device=self.device)
@@ -297,9 +448,15 @@ class Stage2Engine:
         self.x = torch.empty((B * Sp, Dl), dtype=torch.float32, device=dev)
         self.dx = torch.empty((B * Sp, Dl), dtype=torch.float32, device=dev)
         self.vision.workspace(B)
-        if self.pstate is not None:
+        if self.vstate is not None:
+            self.dvis = torch.empty((B * N, Dv), dtype=bf, device=dev)
+            self.vstate.workspace(B)
+        if self.pstate is not None or self.vstate is not None:
             self.dy = torch.empty((B * N, Dl), dtype=bf, device=dev)
-            nb = L.lib().ptk_projector_bwd_bf16_workspace_bytes(self.pstate.c, B * N)
+            lib = L.lib()
+            ws_fn = lib.ptk_projector_bwd_bf16_workspace_bytes if self.vstate is None else \
+                lib.ptk_projector_input_grad_workspace_bytes
+            nb = ws_fn(self._proj_c(), B * N)
             if getattr(self, "_proj_ws", None) is None or self._proj_ws.numel() < nb:
                 self._proj_ws = None
                 self._proj_ws = torch.empty(nb, dtype=torch.uint8, device=dev)
@@ -310,7 +467,20 @@ class Stage2Engine:
             self._ws = torch.empty(n, dtype=torch.uint8, device=dev)
         self._shape = (B, T)
 
-    def _inputs(self, pixel_values, question_ids, answer_ids):
+    def _proj_c(self):
+        """The projector the kernels read: the trained store's, or the frozen module's bf16 shadows."""
+        return self.pstate.c if self.pstate is not None else self.proj.desc()
+
+    def set_vision_trainable(self, on):
+        """Freeze (False) or unfreeze (True) a tower built with train_vision=True.  Frozen, later micro-batches
+        take the frozen forward (no activations kept, no tower backward) and optimizer_step skips the tower; its
+        store, moments and the shared step count are kept.  The hook for the reference's first-epoch-only
+        vision-encoder fine-tune (Stage2/trainer.py:267-289)."""
+        if on and self.vstate is None:
+            raise ValueError("Stage2Engine: set_vision_trainable(True) needs an engine built with train_vision=True")
+        self.vision_trainable = bool(on)
+
+    def _inputs(self, pixel_values, question_ids, answer_ids, train=True):
         """Vision + projector rows of x, token ids and labels, and the batch descriptor."""
         B, Tq = question_ids.shape
         Ta = answer_ids.shape[1]
@@ -323,7 +493,10 @@ class Stage2Engine:
             self.px.copy_(pixel_values)
         else:
             K.cast_bf16(pixel_values.contiguous(), self.px)
-        self.vision.forward_into(self.px, self.vis)
+        if train and self.vision_trainable:   # the same forward, keeping what the tower's backward reads
+            self.vision.forward_train_into(self.px, self.vis, self.vstate)
+        else:
+            self.vision.forward_into(self.px, self.vis)
         if self.pstate is None:
             self.proj.fwd_into(self.vis, self.a, self.h, self.x, out_map=(self.N, 1, self.Sp, -1), round_bf16=True)
         else:   # the same forward from the engine's bf16 store (the parameters the optimizer updates)
@@ -353,21 +526,31 @@ class Stage2Engine:
         else:   # frozen LLM: loss and dX only
             L.check(L.lib().ptk_gemma3_loss_fwd_bwd(cfg, self.llm.c_w, bt, self._ws.data_ptr(), self._ws.numel(),
                                                     stream), "ptk_gemma3_loss_fwd_bwd")
-        if self.pstate is not None:
-            # dy = bf16(dx[vision rows]) (patch 0's row zero), then the four grads accumulated into the bf16 .grad
-            ps, B = self.pstate, question_ids.shape[0]
+        ps, B = self.pstate, question_ids.shape[0]
+        if ps is not None or self.vision_trainable:
+            # dy = bf16(dx[vision rows]) (patch 0's row zero)
             L.check(L.lib().ptk_gather_vision_grad(self.dx.data_ptr(), B, self.N, self.Sp, self.x.shape[1],
                                                    self.dy.data_ptr(), stream), "gather_vision_grad")
-            g = ps.state_dict(grads=True)
+        g = [t.data_ptr() for t in ps.state_dict(grads=True).values()] if ps is not None else [None] * 4
+        if self.vision_trainable:
+            # the projector's four grads (when it is trained) and its input grad d(vis) from one dA, then the
+            # tower's backward: d(last_hidden_state), whose patch-0 rows are zero (dy's are)
+            L.check(L.lib().ptk_projector_input_grad(self._proj_c(), B * self.N, self.vis.data_ptr(),
+                                                     self.a.data_ptr(), self.h.data_ptr(), self.dy.data_ptr(), *g,
+                                                     self.dvis.data_ptr(), self._proj_ws.data_ptr(),
+                                                     self._proj_ws.numel(), stream), "ptk_projector_input_grad")
+            self.vision.backward(self.dvis, self.vstate)
+        elif ps is not None:
+            # the four grads accumulated into the bf16 .grad
             L.check(L.lib().ptk_projector_bwd_bf16(ps.c, B * self.N, self.vis.data_ptr(), self.a.data_ptr(),
-                                                   self.h.data_ptr(), self.dy.data_ptr(),
-                                                   *[g[k].data_ptr() for k in PROJ_KEYS], self._proj_ws.data_ptr(),
-                                                   self._proj_ws.numel(), stream), "ptk_projector_bwd_bf16")
+                                                   self.h.data_ptr(), self.dy.data_ptr(), *g,
+                                                   self._proj_ws.data_ptr(), self._proj_ws.numel(), stream),
+                    "ptk_projector_bwd_bf16")
         return self.loss
 
     def forward_loss(self, pixel_values, question_ids, answer_ids):
         """Validation loss under no_grad (Stage2/trainer.py:518-591): forward + CE only, no grads touched."""
-        cfg, bt = self._inputs(pixel_values, question_ids, answer_ids)
+        cfg, bt = self._inputs(pixel_values, question_ids, answer_ids, train=False)
         L.check(L.lib().ptk_gemma3_loss_fwd(cfg, self.llm.c_w, bt, self._ws.data_ptr(), self._ws.numel(),
                                             L.stream_ptr(self.device)), "ptk_gemma3_loss_fwd")
         return self.loss
@@ -382,6 +565,8 @@ class Stage2Engine:
             self._llm_step(lr)
         if self.pstate is not None:
             self._projector_step(lr)
+        if self.vision_trainable:
+            self._vision_step(lr)
         self.sched_step += self.world
         self.last_lr = lr       # the LR this optimizer step used (param_groups[0]["lr"] during .step())
         return lr
@@ -430,6 +615,25 @@ class Stage2Engine:
         ps.refresh()
         ps.grad.zero_()
 
+    def _vision_step(self, lr):
+        """The tower's own clip + AdamW on its whole store, exactly as _projector_step treats the projector's: one
+        all-reduce of the replicated grads at world > 1, scaled by 1 / world before the sum of squares, the same
+        deterministic step on every rank (Stage2/trainer.py:433-439 clips each trained module separately)."""
+        vs, stream = self.vstate, L.stream_ptr(self.device)
+        scale = 1.0
+        if self.zero1:
+            all_reduce_sum_(vs.grad, self.pg)
+            scale = 1.0 / self.world
+        L.check(L.lib().ptk_bf16_grad_scale_sumsq(vs.grad.data_ptr(), vs.numel, scale, self._partial.data_ptr(),
+                                                  vs.sumsq.data_ptr(), stream), "grad_scale_sumsq")
+        b1, b2 = self.betas
+        L.check(L.lib().ptk_adamw_bf16(vs.flat.data_ptr(), vs.grad.data_ptr(), vs.exp_avg.data_ptr(),
+                                       vs.exp_avg_sq.data_ptr(), vs.numel, vs.sumsq.data_ptr(), self.max_norm, lr,
+                                       b1, b2, self.eps, self.wd, self.opt_step, self.vision_grad_norm.data_ptr(),
+                                       stream), "adamw_bf16")
+        vs.refresh()
+        vs.zero_grad()
+
     @property
     def scheduler_lr(self):
         """lr_scheduler.get_last_lr()[0]: the LR after the scheduler stepped num_processes times per optimizer
@@ -447,6 +651,9 @@ class Stage2Engine:
         if self.pstate is not None:   # the projector's moments, whole on every rank (its store is replicated)
             sd.update(proj_exp_avg=self.pstate.exp_avg.cpu(), proj_exp_avg_sq=self.pstate.exp_avg_sq.cpu(),
                       proj_numel=self.pstate.numel)
+        if self.vstate is not None:   # the tower's moments, whole on every rank too
+            sd.update(vision_exp_avg=self.vstate.exp_avg.cpu(), vision_exp_avg_sq=self.vstate.exp_avg_sq.cpu(),
+                      vision_numel=self.vstate.numel)
         return sd
 
     @property
@@ -455,16 +662,21 @@ class Stage2Engine:
 
     def load_optimizer_state(self, sd):
         pn = self.pstate.numel if self.pstate is not None else 0
-        if (sd["world"], sd["rank"], sd["numel"], sd.get("proj_numel", 0)) != (self.world, self.rank,
-                                                                              self._llm_numel, pn):
+        vn = self.vstate.numel if self.vstate is not None else 0
+        if (sd["world"], sd["rank"], sd["numel"], sd.get("proj_numel", 0), sd.get("vision_numel", 0)) != (
+                self.world, self.rank, self._llm_numel, pn, vn):
             raise ValueError(f"optimizer shard of world {sd['world']} rank {sd['rank']} (store {sd['numel']}, "
-                             f"projector {sd.get('proj_numel', 0)}) does not match this engine (world {self.world} "
-                             f"rank {self.rank} store {self._llm_numel}, projector {pn})")
+                             f"projector {sd.get('proj_numel', 0)}, vision {sd.get('vision_numel', 0)}) does not "
+                             f"match this engine (world {self.world} rank {self.rank} store {self._llm_numel}, "
+                             f"projector {pn}, vision {vn})")
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
         if self.pstate is not None:
             self.pstate.exp_avg.copy_(sd["proj_exp_avg"])
             self.pstate.exp_avg_sq.copy_(sd["proj_exp_avg_sq"])
+        if self.vstate is not None:
+            self.vstate.exp_avg.copy_(sd["vision_exp_avg"])
+            self.vstate.exp_avg_sq.copy_(sd["vision_exp_avg_sq"])
         self.opt_step, self.sched_step = int(sd["step"]), int(sd["sched_step"])
 
     def projector_state_dict(self, grads=False):
@@ -473,6 +685,13 @@ class Stage2Engine:
         if self.pstate is None:
             raise ValueError("Stage2Engine: the projector is frozen (train_projector=False)")
         return self.pstate.state_dict(grads)
+
+
+    def vision_state_dict(self, grads=False):
+        """The trained tower's parameters (or accumulated grads) under HF's names, bf16 on the device."""
+        if self.vstate is None:
+            raise ValueError("Stage2Engine: the vision tower is frozen (train_vision=False)")
+        return self.vstate.state_dict_hf(grads)
 
 
 def synthetic_engine(cfg, device="cuda", seed=0, **kw):

@@ -9,8 +9,10 @@ Supported configurations (the vision encoder frozen, no QLoRA):
   C  freeze_llm=True,  freeze_projection_layer=False  the projector alone, over a frozen LLM
 `freeze_llm=True` with `freeze_projection_layer=True` raises the reference's ValueError ("No trainable
 parameters found", Stage2/trainer.py:242-243); `enable_qlora`, an unfrozen vision encoder and
-`train_ve_first_epoch` raise NotImplementedError (QLoRA/peft needs 4-bit kernels; a trainable vision
-encoder needs its backward pass).  Every flag is checked before any device work.  Note that the reference's
+`train_ve_first_epoch` raise NotImplementedError (QLoRA/peft needs 4-bit kernels; the trained vision encoder
+exists one layer down -- Stage2Engine(train_vision=True) and set_vision_trainable, stage2.py -- but this trainer
+does not drive it yet: its refusal of the two flags is pinned by tests/test_stage2_modes_host.py, and lifting it
+is a follow-up that changes that test).  Every flag is checked before any device work.  Note that the reference's
 own run script ships `ENABLE_QLORA=true` (`Stage2/run_vqa_train_stage2.sh:42`,
 a Qwen3-8B QLoRA run); cfg4 -- the benchmark this path is built for -- is the
 unfrozen-LLM form of the same trainer (`--unfreeze_llm`, `UNFREEZE_LLM` in that
@@ -87,8 +89,9 @@ class VQATrainerStage2:
             raise NotImplementedError("VQATrainerStage2 (HIP): QLoRA / 4-bit LLMs are not supported; run with the "
                                       "dense bf16 LLM and --unfreeze_llm and / or --unfreeze_projection_layer")
         if not freeze_vision_encoder or train_ve_first_epoch:
-            raise NotImplementedError("VQATrainerStage2 (HIP): the vision encoder stays frozen (a trainable SigLIP "
-                                      "needs its backward pass); train the LLM and / or the projector")
+            raise NotImplementedError("VQATrainerStage2 (HIP): the vision encoder stays frozen in this trainer; "
+                                      "train the LLM and / or the projector here, or drive "
+                                      "Stage2Engine(train_vision=True) / set_vision_trainable directly")
         if freeze_llm and freeze_projection_layer:   # Stage2/trainer.py:242-243
             raise ValueError("No trainable parameters found. Check freezing configuration and QLoRA setup.")
         self.train_llm, self.train_projector = not freeze_llm, not freeze_projection_layer
