@@ -613,6 +613,81 @@ size_t ptk_embed_grad_workspace_bytes(int batch, int text_len);
 int ptk_embed_grad(const int64_t* ids, int batch, int text_len, int num_vision, int seq_pad, int hidden, float escale,
                    const float* dx, void* dE, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------ *
+ * The Gemma3 sandwich-norm kernels and the norm weight-grad block of        *
+ * ptk_gemma3_loss_fwd_bwd / ptk_gemma3_train_fwd_bwd (unit-test surface;    *
+ * the model passes call the same launchers internally).                    *
+ * RMSNorm is Gemma3's (modeling_gemma3.py:136-150): fp32 math,              *
+ * rstd = rsqrt(mean(x^2) + eps), scale (1 + w); rms_bwd(x, w, rstd, dn) =   *
+ * dn (1+w) rstd - x rstd^3 sum_c(dn (1+w) x) / cols.  w, rstd are f32;      *
+ * tensors are packed [rows][cols] unless a leading dimension is given.     *
+ * cols: a multiple of 4, <= 3072 (ptk_rms_wgrad: <= 4096); rows <= 2^20.    *
+ * Every argument is checked before any device call (-1 with a message);    *
+ * rows <= 0 with valid sizes returns 0 and launches nothing.  Row maps      *
+ * must have skip == 0.                                                      *
+ * ------------------------------------------------------------------------ */
+
+/* The residual step of the sandwich placement (:412-429): rstd_t[r] of t (bf16); y = bf16(t rstd_t (1 + w_post));
+ * xo (f32) = xi (f32) + y; with w_next != NULL also rstd_x[r] of xo and n (bf16) = bf16(xo rstd_x (1 + w_next)).
+ * w_next == NULL: n and rstd_x are not touched (and may be NULL). */
+int ptk_residual_norm_fwd(const void* t, const float* xi, const float* w_post, const float* w_next, float* xo, void* n,
+                          float* rstd_t, float* rstd_x, int rows, int cols, float eps, void* stream);
+
+/* Its backward, through the function the model calls: dR (f32, in place) += rms_bwd(x2, w_pre, rstd_pre, dn);
+ * dt (bf16) = bf16(rms_bwd(t (bf16), w_post, rstd_t, bf16(dR))) with the updated dR.  mode:
+ *   PTK_RESNORM_BWD_F32       dn f32 (Stage 1 with fp32 output grads); g_pre, g_post, partial unused
+ *   PTK_RESNORM_BWD_BF16      dn bf16; g_pre, g_post, partial unused
+ *   PTK_RESNORM_BWD_WG_FUSED  dn bf16, plus both norms' weight grads from partials the backward kernel writes:
+ *                             g_pre = bf16(g_pre + bf16(sum_r dn x2 rstd_pre)),
+ *                             g_post = bf16(g_post + bf16(sum_r bf16(dR) t rstd_t))   (bf16 [cols], in place)
+ *   PTK_RESNORM_BWD_WG_SPLIT  the same grads from two separate ptk_rms_wgrad passes
+ * partial: ptk_residual_norm_bwd_partial_floats(rows, cols, mode) floats (0 for the first two modes; -1: rows or
+ * cols past the limits). */
+enum { PTK_RESNORM_BWD_F32 = 0, PTK_RESNORM_BWD_BF16 = 1, PTK_RESNORM_BWD_WG_FUSED = 2, PTK_RESNORM_BWD_WG_SPLIT = 3 };
+int64_t ptk_residual_norm_bwd_partial_floats(int rows, int cols, int mode);
+int ptk_residual_norm_bwd(int mode, const float* x2, const float* w_pre, const float* rstd_pre, const void* dn,
+                          float* dR, const void* t, const float* w_post, const float* rstd_t, void* dt, int rows,
+                          int cols, void* g_pre, void* g_post, float* partial, int64_t part_floats, void* stream);
+/* dt (bf16) = bf16(rms_bwd(t (bf16), w, rstd_t, bf16(dR))): the post-norm half alone (the last layer's). */
+int ptk_post_norm_bwd(const float* dR, const void* t, const float* w, const float* rstd_t, void* dt, int rows,
+                      int cols, void* stream);
+/* dx (f32) = dacc + rms_bwd(x (f32), w, rstd, dn (bf16)); dacc NULL (nothing added) or f32, may be dx itself. */
+int ptk_rmsnorm_bwd_bdn(const float* x, const float* w, const float* rstd, const void* dn, const float* dacc,
+                        float* dx, int rows, int cols, void* stream);
+/* ptk_rmsnorm over gathered rows: output row r (y bf16 [rows][cols], rstd[r], rstd may be NULL) is the norm of
+ * row xmap(r) of x (f32, leading dimension ldx >= cols, a multiple of 4). */
+int ptk_rmsnorm_mapped(const float* x, int64_t ldx, ptk_rowmap xmap, const float* w, void* y, float* rstd, int rows,
+                       int cols, float eps, void* stream);
+/* dR[xmap(r)] (f32 [*][cols], in place) += rms_bwd(x[xmap(r)], w, rstd[r], dn[r]) for r < rows (x f32 [*][cols],
+ * dn f32 [rows][cols]); the rows of dR the map does not address are not touched. */
+int ptk_rmsnorm_bwd_scatter(const float* x, ptk_rowmap xmap, const float* w, const float* rstd, const float* dn,
+                            float* dR, int rows, int cols, void* stream);
+
+/* RMSNorm weight grad: grad (bf16 [cols], in place) = bf16(grad + bf16(sum_r dy[r] x[xmap(r)] rstd[r])), the sum
+ * in fp32 in a fixed order (32-row blocks, then 16-row folds).  x f32 or bf16 (x_bf16), dy f32 or bf16 (dy_bf16);
+ * dy_round != 0 rounds an f32 dy to bf16 first.  Instantiated pairs: f32 / f32, bf16 / f32, f32 / bf16 (no
+ * dy_round); any other is an error.  ldx, lddy >= cols, multiples of 4.  partial:
+ * ptk_rms_wgrad_partial_floats(rows, cols) floats of scratch (-1: rows or cols past the limits). */
+int64_t ptk_rms_wgrad_partial_floats(int rows, int cols);
+int ptk_rms_wgrad(const void* x, int x_bf16, int64_t ldx, ptk_rowmap xmap, const float* rstd, const void* dy,
+                  int dy_bf16, int64_t lddy, int dy_round, int rows, int cols, void* grad, float* partial,
+                  int64_t part_floats, void* stream);
+/* The fold alone: grad (bf16 [cols]) = bf16(grad + bf16(sum_b partial[b][c])) over partial f32 [nblk][cols]
+ * (nblk <= 262144, any cols 1..4096), in a fixed order.  partial holds ptk_rms_wgrad_finish_floats(nblk, cols)
+ * floats: the nblk rows, then scratch; both are overwritten. */
+int64_t ptk_rms_wgrad_finish_floats(int nblk, int cols);
+int ptk_rms_wgrad_finish(float* partial, int nblk, int cols, void* grad, int64_t part_floats, void* stream);
+/* q_norm / k_norm weight grads through the rotate-half RoPE (:356-360): for token row r = b * seq + pos and each
+ * head, dn = RoPE^T(dr) with the tables' row pos (cos_t, sin_t f32 [seq][head_dim / 2]);
+ * gq (bf16 [head_dim], in place) = bf16(gq + bf16(sum dn x rstd_q[r][head])), gk likewise over the kv heads.
+ * qkv bf16 [batch * seq][(heads + 2 kv_heads) * head_dim]; dQ bf16 [batch][kv_heads][seq][heads / kv_heads][head_dim];
+ * dK bf16 [batch][kv_heads][seq][head_dim]; rstd_q f32 [rows][heads], rstd_k f32 [rows][kv_heads].  head_dim: a
+ * multiple of 8, <= 256.  partial: ptk_qknorm_wgrad_partial_floats(batch * seq, head_dim) floats. */
+int64_t ptk_qknorm_wgrad_partial_floats(int64_t rows, int head_dim);
+int ptk_qknorm_wgrad(const void* qkv, const float* cos_t, const float* sin_t, int batch, int seq, int heads,
+                     int kv_heads, int head_dim, const float* rstd_q, const float* rstd_k, const void* dQ,
+                     const void* dK, void* gq, void* gk, float* partial, int64_t part_floats, void* stream);
+
 /* clip_grad_norm_ + AdamW over bf16 parameters (Stage2/trainer.py:426-443, optimizer :145-149).
  * ptk_bf16_grad_scale_sumsq: g = bf16(g * scale) in place (scale 1: untouched), *out = sum g^2 (fp32,
  * deterministic; partial: >= ptk_bf16_sumsq_partial_floats() floats).  Sum the *out of every shard / rank

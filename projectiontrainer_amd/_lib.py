@@ -256,6 +256,22 @@ SIGNATURES = {
     "ptk_embed_grad_workspace_bytes": (c_size_t, [c_int, c_int]),
     "ptk_embed_grad": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p,
                                c_size_t, c_void_p]),
+    "ptk_residual_norm_fwd": (c_int, [c_void_p] * 8 + [c_int, c_int, c_float, c_void_p]),
+    "ptk_residual_norm_bwd_partial_floats": (c_int64, [c_int, c_int, c_int]),
+    "ptk_residual_norm_bwd": (c_int, [c_int] + [c_void_p] * 9 + [c_int, c_int, c_void_p, c_void_p, c_void_p, c_int64,
+                                      c_void_p]),
+    "ptk_post_norm_bwd": (c_int, [c_void_p] * 5 + [c_int, c_int, c_void_p]),
+    "ptk_rmsnorm_bwd_bdn": (c_int, [c_void_p] * 6 + [c_int, c_int, c_void_p]),
+    "ptk_rmsnorm_mapped": (c_int, [c_void_p, c_int64, RowMap, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float,
+                                   c_void_p]),
+    "ptk_rmsnorm_bwd_scatter": (c_int, [c_void_p, RowMap] + [c_void_p] * 4 + [c_int, c_int, c_void_p]),
+    "ptk_rms_wgrad_partial_floats": (c_int64, [c_int, c_int]),
+    "ptk_rms_wgrad": (c_int, [c_void_p, c_int, c_int64, RowMap, c_void_p, c_void_p, c_int, c_int64, c_int, c_int,
+                              c_int, c_void_p, c_void_p, c_int64, c_void_p]),
+    "ptk_rms_wgrad_finish_floats": (c_int64, [c_int, c_int]),
+    "ptk_rms_wgrad_finish": (c_int, [c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p]),
+    "ptk_qknorm_wgrad_partial_floats": (c_int64, [c_int64, c_int]),
+    "ptk_qknorm_wgrad": (c_int, [c_void_p] * 3 + [c_int] * 5 + [c_void_p] * 6 + [c_void_p, c_int64, c_void_p]),
     "ptk_bf16_sumsq_partial_floats": (c_int, []),
     "ptk_bf16_grad_scale_sumsq": (c_int, [c_void_p, c_int64, c_float, c_void_p, c_void_p, c_void_p]),
     "ptk_adamw_bf16": (c_int, [c_void_p] * 4 + [c_int64, c_void_p, c_float] + [C.c_double] * 5 +

@@ -146,6 +146,130 @@ int ptk_rmsnorm_bwd(const float* x, const float* w, const float* rstd, const flo
   return launch_rmsnorm_bwd_f32(x, w, rstd, dn, dacc, dx, rows, cols, ST);
 }
 
+// ---- unit-test surface of the Gemma3 norm kernels and the norm weight-grad block: every argument is checked
+// before any device call, then the launcher the model calls runs unchanged
+static int norm_cols_ok(const char* who, int cols) {
+  if (cols <= 0 || cols % 4 || cols > 3072) return set_error("%s: cols %d (multiple of 4, <= 3072)", who, cols);
+  return 0;
+}
+// the norm kernels do not drop rows: a map with skip would index row -1
+static int map_ok(const char* who, ptk_rowmap m) {
+  if (m.g < 0 || m.skip != 0 || m.off < 0 || (m.g > 0 && m.gs < 0))
+    return set_error("%s: row map {g %d, skip %d, gs %lld, off %lld} unsupported", who, m.g, m.skip, (long long)m.gs,
+                     (long long)m.off);
+  return 0;
+}
+
+int ptk_residual_norm_fwd(const void* t, const float* xi, const float* w_post, const float* w_next, float* xo, void* n,
+                          float* rstd_t, float* rstd_x, int rows, int cols, float eps, void* stream) {
+  if (norm_cols_ok("residual_norm_fwd", cols)) return -1;
+  if (rows <= 0) return 0;
+  if (!t || !xi || !w_post || !xo || !rstd_t || (w_next && (!n || !rstd_x)))
+    return set_error("residual_norm_fwd: NULL argument");
+  return launch_residual_norm_fwd((const bf16_t*)t, xi, w_post, w_next, xo, (bf16_t*)n, rstd_t, rstd_x, rows, cols, eps,
+                                  ST);
+}
+int ptk_post_norm_bwd(const float* dR, const void* t, const float* w, const float* rstd_t, void* dt, int rows,
+                      int cols, void* stream) {
+  if (norm_cols_ok("post_norm_bwd", cols)) return -1;
+  if (rows <= 0) return 0;
+  if (!dR || !t || !w || !rstd_t || !dt) return set_error("post_norm_bwd: NULL argument");
+  return launch_post_norm_bwd(dR, (const bf16_t*)t, w, rstd_t, (bf16_t*)dt, rows, cols, ST);
+}
+int ptk_rmsnorm_bwd_bdn(const float* x, const float* w, const float* rstd, const void* dn, const float* dacc,
+                        float* dx, int rows, int cols, void* stream) {
+  if (norm_cols_ok("rmsnorm_bwd_bdn", cols)) return -1;
+  if (rows <= 0) return 0;
+  if (!x || !w || !rstd || !dn || !dx) return set_error("rmsnorm_bwd_bdn: NULL argument");
+  return launch_rmsnorm_bwd_bdn(x, w, rstd, (const bf16_t*)dn, dacc, dx, rows, cols, ST);
+}
+int ptk_rmsnorm_mapped(const float* x, int64_t ldx, ptk_rowmap xmap, const float* w, void* y, float* rstd, int rows,
+                       int cols, float eps, void* stream) {
+  if (norm_cols_ok("rmsnorm_mapped", cols) || map_ok("rmsnorm_mapped", xmap)) return -1;
+  if (ldx < cols || ldx % 4) return set_error("rmsnorm_mapped: ldx %lld (>= cols %d, multiple of 4)", (long long)ldx, cols);
+  if (rows <= 0) return 0;
+  if (!x || !w || !y) return set_error("rmsnorm_mapped: NULL argument");
+  return launch_rmsnorm_fwd(x, (long)ldx, to_map(xmap), w, (bf16_t*)y, rstd, rows, cols, eps, ST);
+}
+int ptk_rmsnorm_bwd_scatter(const float* x, ptk_rowmap xmap, const float* w, const float* rstd, const float* dn,
+                            float* dR, int rows, int cols, void* stream) {
+  if (norm_cols_ok("rmsnorm_bwd_scatter", cols) || map_ok("rmsnorm_bwd_scatter", xmap)) return -1;
+  if (rows <= 0) return 0;
+  if (!x || !w || !rstd || !dn || !dR) return set_error("rmsnorm_bwd_scatter: NULL argument");
+  return launch_rmsnorm_bwd_scatter(x, to_map(xmap), w, rstd, dn, dR, rows, cols, ST);
+}
+
+// the surface takes at most 2^20 rows (the launchers' int partial sizes stay far below 2^31)
+constexpr int kSurfaceMaxRows = 1 << 20;
+int64_t ptk_rms_wgrad_partial_floats(int rows, int cols) {
+  if (rows > kSurfaceMaxRows || cols > 4096) return -1;
+  return rows > 0 && cols > 0 ? (int64_t)rms_wgrad_partial_floats(rows, cols) : 0;
+}
+int ptk_rms_wgrad(const void* x, int x_bf16, int64_t ldx, ptk_rowmap xmap, const float* rstd, const void* dy,
+                  int dy_bf16, int64_t lddy, int dy_round, int rows, int cols, void* grad, float* partial,
+                  int64_t part_floats, void* stream) {
+  if (cols <= 0 || cols % 4 || cols > 4096) return set_error("rms_wgrad: cols %d (multiple of 4, <= 4096)", cols);
+  if (map_ok("rms_wgrad", xmap)) return -1;
+  if (ldx < cols || ldx % 4 || lddy < cols || lddy % 4)
+    return set_error("rms_wgrad: ldx %lld / lddy %lld (>= cols %d, multiples of 4)", (long long)ldx, (long long)lddy,
+                     cols);
+  if (x_bf16 && dy_bf16) return set_error("rms_wgrad: x bf16 with dy bf16 is not instantiated");
+  if (dy_bf16 && dy_round) return set_error("rms_wgrad: dy_round with a bf16 dy");
+  if (rows > kSurfaceMaxRows) return set_error("rms_wgrad: %d rows (max %d)", rows, kSurfaceMaxRows);
+  if (rows <= 0) return 0;
+  if (!x || !rstd || !dy || !grad || !partial) return set_error("rms_wgrad: NULL argument");
+  if (part_floats < ptk_rms_wgrad_partial_floats(rows, cols))
+    return set_error("rms_wgrad: partial %lld floats < %lld", (long long)part_floats,
+                     (long long)ptk_rms_wgrad_partial_floats(rows, cols));
+  const RowMap m = to_map(xmap);
+  if (x_bf16)
+    return launch_rms_wgrad_bx((const bf16_t*)x, (long)ldx, m, rstd, (const float*)dy, (long)lddy, dy_round != 0, rows,
+                               cols, (bf16_t*)grad, partial, ST);
+  if (dy_bf16)
+    return launch_rms_wgrad_bdy((const float*)x, (long)ldx, m, rstd, (const bf16_t*)dy, (long)lddy, rows, cols,
+                                (bf16_t*)grad, partial, ST);
+  return launch_rms_wgrad((const float*)x, (long)ldx, m, rstd, (const float*)dy, (long)lddy, dy_round != 0, rows, cols,
+                          (bf16_t*)grad, partial, ST);
+}
+int64_t ptk_rms_wgrad_finish_floats(int nblk, int cols) {
+  if (nblk > (1 << 18) || cols > 4096) return -1;
+  return nblk > 0 && cols > 0 ? (int64_t)rms_wgrad_finish_floats(nblk, cols) : 0;
+}
+int ptk_rms_wgrad_finish(float* partial, int nblk, int cols, void* grad, int64_t part_floats, void* stream) {
+  if (cols <= 0 || cols > 4096) return set_error("rms_wgrad_finish: cols %d (1 .. 4096)", cols);
+  if (nblk > (1 << 18)) return set_error("rms_wgrad_finish: %d partial rows (max 262144)", nblk);
+  if (nblk <= 0) return 0;
+  if (!partial || !grad) return set_error("rms_wgrad_finish: NULL argument");
+  if (part_floats < ptk_rms_wgrad_finish_floats(nblk, cols))
+    return set_error("rms_wgrad_finish: partial %lld floats < %lld", (long long)part_floats,
+                     (long long)ptk_rms_wgrad_finish_floats(nblk, cols));
+  return launch_rms_wgrad_finish(partial, nblk, cols, (bf16_t*)grad, ST);
+}
+int64_t ptk_qknorm_wgrad_partial_floats(int64_t rows, int head_dim) {
+  if (rows > kSurfaceMaxRows || head_dim > 256) return -1;
+  return rows > 0 && head_dim > 0 ? (int64_t)qknorm_wgrad_partial_floats((long)rows, head_dim) : 0;
+}
+int ptk_qknorm_wgrad(const void* qkv, const float* cos_t, const float* sin_t, int batch, int seq, int heads,
+                     int kv_heads, int head_dim, const float* rstd_q, const float* rstd_k, const void* dQ,
+                     const void* dK, void* gq, void* gk, float* partial, int64_t part_floats, void* stream) {
+  if (head_dim <= 0 || head_dim > 256 || head_dim % 8)
+    return set_error("qknorm_wgrad: head_dim %d (multiple of 8, <= 256)", head_dim);
+  if (heads <= 0 || kv_heads <= 0 || heads % kv_heads)
+    return set_error("qknorm_wgrad: heads %d / kv_heads %d", heads, kv_heads);
+  if (batch < 0 || seq < 0 || (int64_t)batch * seq > kSurfaceMaxRows)
+    return set_error("qknorm_wgrad: batch %d x seq %d", batch, seq);
+  const int64_t M = (int64_t)batch * seq;
+  if (M == 0) return 0;
+  if (!qkv || !cos_t || !sin_t || !rstd_q || !rstd_k || !dQ || !dK || !gq || !gk || !partial)
+    return set_error("qknorm_wgrad: NULL argument");
+  if (part_floats < ptk_qknorm_wgrad_partial_floats(M, head_dim))
+    return set_error("qknorm_wgrad: partial %lld floats < %lld", (long long)part_floats,
+                     (long long)ptk_qknorm_wgrad_partial_floats(M, head_dim));
+  const AttnShape sh{batch, seq, heads, kv_heads, head_dim};
+  return launch_qknorm_wgrad((const bf16_t*)qkv, cos_t, sin_t, sh, rstd_q, rstd_k, (const bf16_t*)dQ, (const bf16_t*)dK,
+                             (bf16_t*)gq, (bf16_t*)gk, partial, ST);
+}
+
 int ptk_qknorm_rope_fwd(const void* qkv, const float* q_norm_w, const float* k_norm_w, const float* cos_t,
                         const float* sin_t, int batch, int seq, int heads, int kv_heads, int head_dim, float eps,
                         void* Q, void* K, void* V, float* rstd_q, float* rstd_k, void* stream) {

@@ -71,12 +71,15 @@ static bool geglu_split() {
 static bool norm_wg_fused() { return PTK_AB("PTK_NORM_WG", 1) != 0; }
 
 // dR += rms_bwd(x2, w_pre, rstd_pre, dn); dt = bf16(rms_bwd(t, w_post, rstd_t, bf16(dR))); with g_pre / g_post
-// (Stage 2) also accumulates both norms' weight grads.  wpart: the fused kernel's two partial sets back to back
+// (Stage 2) also accumulates both norms' weight grads.  fused: from the partials the backward kernel itself writes
+// (wpart: its two partial sets back to back), else from the two separate rms_wgrad passes (the model passes
+// norm_wg_fused(); ptk_residual_norm_bwd picks either)
 static int residual_norm_bwd_grads(const float* x2, const float* w_pre, const float* rstd_pre, const bf16_t* dn,
                                    float* dR, const bf16_t* t, const float* w_post, const float* rstd_t, bf16_t* dt,
-                                   int M, int H, bf16_t* g_pre, bf16_t* g_post, float* wpart, hipStream_t st) {
+                                   int M, int H, bf16_t* g_pre, bf16_t* g_post, float* wpart, bool fused,
+                                   hipStream_t st) {
   const RowMap ident{0, 0, 0, 0};
-  if (g_pre && norm_wg_fused()) {
+  if (g_pre && fused) {
     const int nb = residual_norm_bwd_wg_blocks(M);
     float* pq = wpart + rms_wgrad_finish_floats(nb, H);
     CK(launch_residual_norm_bwd_wg(x2, w_pre, rstd_pre, dn, dR, t, w_post, rstd_t, dt, M, H, wpart, pq, st));
@@ -959,7 +962,7 @@ int gemma_run(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, const pt
     sq.next("gemma.bwd.attn");
     CK(residual_norm_bwd_grads(sv.x2, L.ln_pre_ff, sv.rstd_pre, w.dtmp, dR, sv.ao, L.ln_post_attn, sv.rstd_ao, w.dao,
                                M, H, train ? (bf16_t*)GL->ln_pre_ff : nullptr,
-                               train ? (bf16_t*)GL->ln_post_attn : nullptr, w.wpart, st));
+                               train ? (bf16_t*)GL->ln_post_attn : nullptr, w.wpart, norm_wg_fused(), st));
     if (train)
       CK(weight_grad(w.dao, H, ident, H, sv.O, Dq, ident, Dq, M, w.TA, w.TB, GL->wo, w.skpart, w.sk_floats, st));
     {  // dO (Q layout) = dao . Wo, one GEMM per kv head group of output columns
@@ -1000,7 +1003,8 @@ int gemma_run(const ptk_gemma3_config* c, const ptk_gemma3_weights* wt, const pt
       const GemmaLayerSave& sp = w.L[l - 1];
       CK(residual_norm_bwd_grads(w.x[l], L.ln_in, sv.rstd_in, w.dtmp, dR, sp.dn, Lp.ln_post_ff, sp.rstd_dn, w.dao,
                                  M, H, train ? (bf16_t*)GL->ln_in : nullptr,
-                                 train ? (bf16_t*)gr->layers[l - 1].ln_post_ff : nullptr, w.wpart, st));
+                                 train ? (bf16_t*)gr->layers[l - 1].ln_post_ff : nullptr, w.wpart, norm_wg_fused(),
+                                 st));
     } else {
       if (train)
         CK(launch_rms_wgrad_bdy(w.x[l], H, ident, sv.rstd_in, w.dtmp, H, M, H, (bf16_t*)GL->ln_in, w.wpart, st));
@@ -1572,6 +1576,43 @@ int ptk_embed_grad(const int64_t* ids, int batch, int text_len, int num_vision, 
     return set_error("embed_grad: workspace %zu bytes < %zu", ws_bytes, embed_grad_ws_bytes(batch, text_len));
   return launch_embed_grad(ids, batch, text_len, num_vision, seq_pad, hidden, escale, dx, (bf16_t*)dE, ws,
                            (hipStream_t)stream);
+}
+
+// weight-grad partials of ptk_residual_norm_bwd: the fused kernel's two partial sets with their fold scratch, or
+// the one set the two separate passes share (what gemma_train sizes w.wpart from)
+int64_t ptk_residual_norm_bwd_partial_floats(int rows, int cols, int mode) {
+  if (rows > (1 << 20) || cols > 3072) return -1;   // the surface's row limit (int partial sizes)
+  if (rows <= 0 || cols <= 0) return 0;
+  if (mode == PTK_RESNORM_BWD_WG_FUSED) return 2 * (int64_t)rms_wgrad_finish_floats(residual_norm_bwd_wg_blocks(rows), cols);
+  if (mode == PTK_RESNORM_BWD_WG_SPLIT) return rms_wgrad_partial_floats(rows, cols);
+  return 0;
+}
+
+int ptk_residual_norm_bwd(int mode, const float* x2, const float* w_pre, const float* rstd_pre, const void* dn,
+                          float* dR, const void* t, const float* w_post, const float* rstd_t, void* dt, int rows,
+                          int cols, void* g_pre, void* g_post, float* partial, int64_t part_floats, void* stream) {
+  if (mode < PTK_RESNORM_BWD_F32 || mode > PTK_RESNORM_BWD_WG_SPLIT)
+    return set_error("residual_norm_bwd: mode %d", mode);
+  if (cols <= 0 || cols % 4 || cols > 3072)
+    return set_error("residual_norm_bwd: cols %d (multiple of 4, <= 3072)", cols);
+  if (rows > (1 << 20)) return set_error("residual_norm_bwd: %d rows (max %d)", rows, 1 << 20);
+  if (rows <= 0) return 0;
+  if (!x2 || !w_pre || !rstd_pre || !dn || !dR || !t || !w_post || !rstd_t || !dt)
+    return set_error("residual_norm_bwd: NULL argument");
+  const bool wg = mode == PTK_RESNORM_BWD_WG_FUSED || mode == PTK_RESNORM_BWD_WG_SPLIT;
+  if (wg) {
+    if (!g_pre || !g_post || !partial) return set_error("residual_norm_bwd: NULL weight grad or partial buffer");
+    const int64_t need = ptk_residual_norm_bwd_partial_floats(rows, cols, mode);
+    if (part_floats < need)
+      return set_error("residual_norm_bwd: partial %lld floats < %lld", (long long)part_floats, (long long)need);
+  }
+  if (mode == PTK_RESNORM_BWD_F32)
+    return launch_residual_norm_bwd(x2, w_pre, rstd_pre, (const float*)dn, dR, (const bf16_t*)t, w_post, rstd_t,
+                                    (bf16_t*)dt, rows, cols, (hipStream_t)stream);
+  return residual_norm_bwd_grads(x2, w_pre, rstd_pre, (const bf16_t*)dn, dR, (const bf16_t*)t, w_post, rstd_t,
+                                 (bf16_t*)dt, rows, cols, wg ? (bf16_t*)g_pre : nullptr,
+                                 wg ? (bf16_t*)g_post : nullptr, partial, mode == PTK_RESNORM_BWD_WG_FUSED,
+                                 (hipStream_t)stream);
 }
 
 int ptk_bf16_grad_scale_sumsq(void* g, int64_t n, float scale, float* partial, float* out, void* stream) {

@@ -134,6 +134,65 @@ int main(int argc, char** argv) {
   EXPECT(ptk_projector_bwd_allreduce(&pj, 1, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, comm, nullptr,
                                      nullptr) != 0);
 
+  // the norm / norm weight-grad unit-test surface: every refusal comes before any launch (tests/test_norm_surface_host.py)
+  {
+    float h[64] = {0};
+    void* p = h;
+    float* f = h;
+    const ptk_rowmap ident{0, 0, 0, 0}, skip{4, 1, 8, 0};
+    for (int cols : {0, 1154, 3076}) {
+      EXPECT(ptk_residual_norm_fwd(p, f, f, f, f, p, f, f, 4, cols, 1e-6f, nullptr) == -1);
+      EXPECT(strstr(ptk_last_error(), "cols") != nullptr);
+      for (int mode = 0; mode < 4; ++mode)
+        EXPECT(ptk_residual_norm_bwd(mode, f, f, f, p, f, p, f, f, p, 4, cols, p, p, f, (int64_t)1 << 40, nullptr) == -1);
+      EXPECT(ptk_post_norm_bwd(f, p, f, f, p, 4, cols, nullptr) == -1);
+      EXPECT(ptk_rmsnorm_bwd_bdn(f, f, f, p, nullptr, f, 4, cols, nullptr) == -1);
+      EXPECT(ptk_rmsnorm_mapped(f, 4096, ident, f, p, f, 4, cols, 1e-6f, nullptr) == -1);
+      EXPECT(ptk_rmsnorm_bwd_scatter(f, ident, f, f, f, f, 4, cols, nullptr) == -1);
+    }
+    EXPECT(ptk_residual_norm_fwd(p, f, f, f, f, p, f, f, 0, 1152, 1e-6f, nullptr) == 0);
+    EXPECT(ptk_residual_norm_fwd(nullptr, f, f, f, f, p, f, f, 4, 1152, 1e-6f, nullptr) == -1);
+    EXPECT(ptk_residual_norm_bwd(2, f, f, f, p, f, p, f, f, p, 0, 1152, p, p, f, 0, nullptr) == 0);
+    EXPECT(ptk_residual_norm_bwd(7, f, f, f, p, f, p, f, f, p, 4, 8, p, p, f, 64, nullptr) == -1);
+    for (int mode : {PTK_RESNORM_BWD_WG_FUSED, PTK_RESNORM_BWD_WG_SPLIT}) {
+      const int64_t need = ptk_residual_norm_bwd_partial_floats(37, 1152, mode);
+      EXPECT(need > 0);
+      EXPECT(ptk_residual_norm_bwd(mode, f, f, f, p, f, p, f, f, p, 37, 1152, p, p, f, need - 1, nullptr) == -1);
+      EXPECT(strstr(ptk_last_error(), "partial") != nullptr);
+      EXPECT(ptk_residual_norm_bwd(mode, f, f, f, p, f, p, f, f, p, 37, 1152, p, nullptr, f, need, nullptr) == -1);
+    }
+    EXPECT(ptk_rmsnorm_mapped(f, 8, skip, f, p, f, 4, 8, 1e-6f, nullptr) == -1);
+    EXPECT(ptk_rmsnorm_mapped(f, 4, ident, f, p, f, 4, 8, 1e-6f, nullptr) == -1);
+    EXPECT(ptk_rmsnorm_bwd_scatter(f, skip, f, f, f, f, 4, 8, nullptr) == -1);
+    for (int cols : {0, 1154, 4100})
+      EXPECT(ptk_rms_wgrad(p, 0, 4104, ident, f, p, 0, 4104, 1, 4, cols, p, f, (int64_t)1 << 40, nullptr) == -1);
+    EXPECT(ptk_rms_wgrad(p, 0, 8, ident, f, p, 0, 8, 1, 0, 8, p, f, 0, nullptr) == 0);
+    EXPECT(ptk_rms_wgrad(p, 1, 8, ident, f, p, 1, 8, 0, 4, 8, p, f, 64, nullptr) == -1);      // bf16 / bf16
+    EXPECT(ptk_rms_wgrad(p, 0, 8, ident, f, p, 1, 8, 1, 4, 8, p, f, 64, nullptr) == -1);      // dy_round on bf16 dy
+    EXPECT(ptk_rms_wgrad(p, 0, 4, ident, f, p, 0, 8, 1, 4, 8, p, f, 64, nullptr) == -1);      // ldx < cols
+    EXPECT(ptk_rms_wgrad(p, 0, 8, skip, f, p, 0, 8, 1, 4, 8, p, f, 64, nullptr) == -1);
+    EXPECT(ptk_rms_wgrad(nullptr, 0, 8, ident, f, p, 0, 8, 1, 4, 8, p, f, 64, nullptr) == -1);
+    EXPECT(ptk_rms_wgrad(p, 0, 1152, ident, f, p, 0, 1152, 1, 130, 1152, p, f, ptk_rms_wgrad_partial_floats(130, 1152) - 1,
+                         nullptr) == -1);
+    EXPECT(ptk_rms_wgrad_finish(f, 4, 0, p, 64, nullptr) == -1);
+    EXPECT(ptk_rms_wgrad_finish(f, 0, 64, p, 0, nullptr) == 0);
+    EXPECT(ptk_rms_wgrad_finish(nullptr, 4, 64, p, 1 << 20, nullptr) == -1);
+    EXPECT(ptk_rms_wgrad_finish(f, 257, 100, p, ptk_rms_wgrad_finish_floats(257, 100) - 1, nullptr) == -1);
+    for (int D : {264, 12, 0}) {
+      EXPECT(ptk_qknorm_wgrad(p, f, f, 3, 37, 4, 1, D, f, f, p, p, p, p, f, (int64_t)1 << 40, nullptr) == -1);
+      EXPECT(strstr(ptk_last_error(), "head_dim") != nullptr);
+    }
+    EXPECT(ptk_qknorm_wgrad(p, f, f, 3, 37, 4, 3, 64, f, f, p, p, p, p, f, (int64_t)1 << 40, nullptr) == -1);
+    EXPECT(ptk_qknorm_wgrad(p, f, f, 0, 37, 4, 1, 64, f, f, p, p, p, p, f, 0, nullptr) == 0);
+    EXPECT(ptk_qknorm_wgrad(nullptr, f, f, 3, 37, 4, 1, 64, f, f, p, p, p, p, f, (int64_t)1 << 40, nullptr) == -1);
+    EXPECT(ptk_qknorm_wgrad(p, f, f, 3, 37, 4, 1, 256, f, f, p, p, p, p, f, ptk_qknorm_wgrad_partial_floats(111, 256) - 1,
+                            nullptr) == -1);
+    EXPECT(ptk_rms_wgrad_finish_floats(17, 100) == (17 + 2) * 100);
+    EXPECT(ptk_rms_wgrad_partial_floats(130, 1152) == (5 + 1) * 1152);
+    EXPECT(ptk_qknorm_wgrad_partial_floats(111, 256) == (2 * 14 + 1) * 256);
+    for (float v : h) EXPECT(v == 0.f);
+  }
+
   // dispatch census and stage timers (timers off: begin / end pair up without recording)
   std::vector<int64_t> counts(PTK_GEMM_NPATHS * 8, -1);
   EXPECT(ptk_gemm_path_counts(counts.data(), 1) == 0);
