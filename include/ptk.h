@@ -160,6 +160,38 @@ int ptk_softmax(const float* S, void* P, int nz, int rows, int cols, int64_t ld,
  * row_loss[r] = lse - logit[t]; logits overwritten with (softmax - onehot) * gscale[0]. */
 int ptk_cross_entropy(void* logits, int64_t ld, int rows, int vocab, const int64_t* targets, float* row_loss,
                       const float* gscale, void* stream);
+/* The loss head piece by piece, for tests: the launchers ptk_gemma3_*_fwd_bwd calls, behind argument checks that run
+ * before any device call (-1 with a message naming the argument).
+ *
+ * Labels.  ptk_count_valid counts label != -100 (torch's ignore_index), while both cross-entropy kernels treat
+ * target < 0 as ignored (row_loss 0, d(logits) 0 over the whole row) and read logits[target] unchecked otherwise:
+ * every target must be -100 or lie in [0, vocab).  Any other value is the caller's error (another negative value
+ * is counted but contributes nothing; a value >= vocab reads out of bounds).
+ *
+ * ptk_gemm_row_stats: ptk_gemm (under the current ptk_gemm_force_small_tiles mode) that also writes, for each row r
+ * < M and each 64-column chunk k, the pair (max, sum exp(x - max)) over the bf16 logits it stores in columns
+ * 64k .. 64k + 63, as two floats at stats[r * ld_stats + 2k]; a chunk that is all -inf gets (-inf, NaN).  Rows >=
+ * M and the floats past 2 * N / 64 of a row are not written.  Refused, because the statistics would be left
+ * unwritten or would not describe the stored logits: act != PTK_ACT_NONE, out != PTK_OUT_BF16, batch != 1, N % 64,
+ * ldc % 8 or ldc < N, a C that is not 16-byte aligned, bias / rowadd / resid / resid16 / aux / aux2 / aux_in /
+ * aux_in2, a non-identity cmap, alpha != 1, the *_kt flags, ld_stats odd or < 2 * N / 64, stats NULL or not 8-byte
+ * aligned.  (The same check guards every internal launch that asks for the statistics.)
+ *
+ * ptk_cross_entropy_stats: ptk_cross_entropy from those statistics (the logits are read once): vocab % 64 == 0,
+ * ld % 8 == 0, ld >= vocab, ld_stats even and >= 2 * vocab / 64; rows <= 0 returns 0 and launches nothing.  A NaN
+ * chunk max makes that row's loss NaN.
+ *
+ * ptk_count_valid: count[0] = number of labels != -100 among n (exact in fp32 up to 2^24), gscale[0] = loss_scale /
+ * count[0], or 0 when the count is 0.  n <= 0 counts nothing: count[0] = 0 and gscale[0] = 0 are written (labels
+ * may then be NULL).
+ *
+ * ptk_loss_reduce: loss[0] = sum(row_loss[0 .. rows)) / count[0], NaN when count[0] <= 0 (the mean over no valid
+ * target, as torch gives).  rows <= 0 sums nothing: loss[0] = 0 / count[0], or NaN (row_loss may then be NULL). */
+int ptk_gemm_row_stats(const ptk_gemm_desc* d, float* stats, int64_t ld_stats, void* stream);
+int ptk_cross_entropy_stats(void* logits, int64_t ld, int rows, int vocab, const float* stats, int64_t ld_stats,
+                            const int64_t* targets, float* row_loss, const float* gscale, void* stream);
+int ptk_count_valid(const int64_t* labels, int n, float loss_scale, float* gscale, float* count, void* stream);
+int ptk_loss_reduce(const float* row_loss, int rows, const float* count, float* loss, void* stream);
 int ptk_transpose_bf16(const void* in, int64_t ld_in, void* out, int64_t ld_out, int nz, int64_t s_in,
                        int64_t s_out, int rows, int cols, int rows_pad, void* stream);
 /* Stage-2 weight-grad operand transpose with a row gather: out[c][r] = in[map(r)][c] for r < rows, 0 for

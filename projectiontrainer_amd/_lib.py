@@ -166,6 +166,11 @@ SIGNATURES = {
     "ptk_softmax": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int64, c_int, c_int, c_int, c_int,
                             c_int, c_void_p, c_int, c_void_p]),
     "ptk_cross_entropy": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "ptk_gemm_row_stats": (c_int, [C.POINTER(GemmDesc), c_void_p, c_int64, c_void_p]),
+    "ptk_cross_entropy_stats": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p,
+                                        c_void_p, c_void_p]),
+    "ptk_count_valid": (c_int, [c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p]),
+    "ptk_loss_reduce": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "ptk_transpose_bf16": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int, c_int64, c_int64, c_int,
                                    c_int, c_int, c_void_p]),
     "ptk_transpose_rows_bf16": (c_int, [c_void_p, c_int64, c_int, c_int64, c_int64, c_int, c_int, c_void_p, c_int64,

@@ -297,6 +297,43 @@ int ptk_cross_entropy(void* logits, int64_t ld, int rows, int vocab, const int64
   return launch_ce_fwd_bwd((bf16_t*)logits, ld, rows, vocab, targets, row_loss, gscale, ST);
 }
 
+// ---- unit-test surface of the loss head (the lm_head GEMM's softmax statistics, the CE pass that reads them, the
+// valid-label count and the loss mean): every argument is checked before any device call, then the launcher the
+// model calls runs unchanged
+int ptk_gemm_row_stats(const ptk_gemm_desc* d, float* stats, int64_t ld_stats, void* stream) {
+  if (!d) return set_error("ptk_gemm_row_stats: null desc");
+  if (!stats) return set_error("ptk_gemm_row_stats: NULL stats");
+  if (!d->A || !d->B || !d->C) return set_error("ptk_gemm_row_stats: NULL operand (A, B or C)");
+  GemmArgs a = to_args(d);
+  a.row_stats = stats;
+  a.ld_stats = (long)ld_stats;
+  return launch_gemm(a, d->act, d->out, d->batch > 0 ? d->batch : 1, ST);   // (row_stats_check: the refusals)
+}
+int ptk_cross_entropy_stats(void* logits, int64_t ld, int rows, int vocab, const float* stats, int64_t ld_stats,
+                            const int64_t* targets, float* row_loss, const float* gscale, void* stream) {
+  if (vocab <= 0 || vocab % 64) return set_error("cross_entropy_stats: vocab %d must be a positive multiple of 64", vocab);
+  if (ld % 8 || ld < vocab)
+    return set_error("cross_entropy_stats: ld %lld (>= vocab %d, a multiple of 8)", (long long)ld, vocab);
+  if (ld_stats < 2LL * (vocab / 64))
+    return set_error("cross_entropy_stats: ld_stats %lld < 2 * vocab / 64 = %d", (long long)ld_stats, 2 * (vocab / 64));
+  if (rows <= 0) return 0;
+  if (!logits || !stats || !targets || !row_loss || !gscale) return set_error("cross_entropy_stats: NULL argument");
+  if (((uintptr_t)logits & 15) || ((uintptr_t)stats & 7) || (ld_stats & 1))
+    return set_error("cross_entropy_stats: logits must be 16-byte aligned, stats 8-byte aligned with an even ld_stats");
+  return launch_ce_stats_fwd_bwd((bf16_t*)logits, (long)ld, rows, vocab, stats, (long)ld_stats, targets, row_loss,
+                                 gscale, ST);
+}
+int ptk_count_valid(const int64_t* labels, int n, float loss_scale, float* gscale, float* count, void* stream) {
+  if (!gscale || !count) return set_error("count_valid: NULL gscale / count");
+  if (n > 0 && !labels) return set_error("count_valid: NULL labels");
+  return launch_count_valid(labels, n > 0 ? n : 0, loss_scale, gscale, count, ST);
+}
+int ptk_loss_reduce(const float* row_loss, int rows, const float* count, float* loss, void* stream) {
+  if (!count || !loss) return set_error("loss_reduce: NULL count / loss");
+  if (rows > 0 && !row_loss) return set_error("loss_reduce: NULL row_loss");
+  return launch_loss_reduce(row_loss, rows > 0 ? rows : 0, count, loss, ST);
+}
+
 int ptk_transpose_bf16(const void* in, int64_t ld_in, void* out, int64_t ld_out, int nz, int64_t s_in, int64_t s_out,
                        int rows, int cols, int rows_pad, void* stream) {
   return launch_transpose((const bf16_t*)in, ld_in, s_in, 0, 1, (bf16_t*)out, ld_out, s_out, 0, nz, rows, cols,

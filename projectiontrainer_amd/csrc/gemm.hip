@@ -786,6 +786,33 @@ GemmPlanEnv gemm_plan_env() {
   return e;
 }
 
+// GemmArgs::row_stats: the softmax statistics are written only on the epilogue's 8-column bf16 branch, from the
+// scaled accumulators alone and at the unmapped row, so every operand under which that branch is not taken, or
+// under which the stored logits would differ from the values the statistics describe, is an error here instead
+// of statistics left unwritten (the cross-entropy pass would read garbage)
+static int row_stats_check(const GemmArgs& a, int act, int out, int batch) {
+  if (act != ACT_NONE) return set_error("gemm row_stats: act %d (PTK_ACT_NONE only)", act);
+  if (out != OUT_BF16) return set_error("gemm row_stats: out %d (PTK_OUT_BF16 only)", out);
+  if (batch != 1) return set_error("gemm row_stats: batch %d (1 only)", batch);
+  if (a.N % 64) return set_error("gemm row_stats: N %d must be a multiple of 64", a.N);
+  if (a.ldc % 8 || a.ldc < a.N) return set_error("gemm row_stats: ldc %ld (>= N %d, a multiple of 8)", a.ldc, a.N);
+  if ((uintptr_t)a.C & 15) return set_error("gemm row_stats: C must be 16-byte aligned");
+  if (a.bias) return set_error("gemm row_stats: bias is not reflected in the statistics");
+  if (a.rowadd) return set_error("gemm row_stats: rowadd is not reflected in the statistics");
+  if (a.resid) return set_error("gemm row_stats: resid is not reflected in the statistics");
+  if (a.resid16) return set_error("gemm row_stats: resid16 is not reflected in the statistics");
+  if (a.aux || a.aux2) return set_error("gemm row_stats: aux outputs are not supported");
+  if (a.aux_in || a.aux_in2) return set_error("gemm row_stats: aux_in inputs are not supported");
+  if (a.cmap.g != 0 || a.cmap.skip != 0 || a.cmap.gs != 0 || a.cmap.off != 0)
+    return set_error("gemm row_stats: cmap must be the identity (the statistics are stored at the unmapped row)");
+  if (a.alpha != 1.f) return set_error("gemm row_stats: alpha %g (1 only)", (double)a.alpha);
+  if (a.a_kt || a.c_kt || a.aux_kt || a.aux_in_kt) return set_error("gemm row_stats: k-step-tiled operands");
+  if (a.ld_stats < 2L * (a.N / 64) || (a.ld_stats & 1))
+    return set_error("gemm row_stats: ld_stats %ld (even, >= 2 * N / 64 = %ld)", a.ld_stats, 2L * (a.N / 64));
+  if ((uintptr_t)a.row_stats & 7) return set_error("gemm row_stats: stats must be 8-byte aligned");
+  return 0;
+}
+
 // plan (gemm_plan.cpp: the shape rule) -> launch
 int launch_gemm(const GemmArgs& a, int act, int out, int batch, hipStream_t st, const GemmPlan* planned) {
   if (a.M <= 0 || a.N <= 0 || batch <= 0) return 0;
@@ -799,6 +826,7 @@ int launch_gemm(const GemmArgs& a, int act, int out, int batch, hipStream_t st, 
   // the GELU-tanh epilogues store the pre-activation at C's own offsets (the persistent ones address it through C's)
   if (act == ACT_GELU_TANH && a.aux && (a.ld_aux != a.ldc || a.cmap.g != 0 || a.cmap.off != 0))
     return set_error("gemm: a GELU-tanh pre-activation output needs ld_aux == ldc and an identity C row map");
+  if (a.row_stats && row_stats_check(a, act, out, batch)) return -1;
   const GemmPlan plan = planned ? *planned : gemm_plan(a, act, out, batch, gemm_plan_env());
   // k-step-tiled activations are the operands' contract: no family but the one with the variant may run them
   if (a.a_kt && !a_ktiled_ok(a, plan, act, out, batch, lean_epilogue_enabled()))

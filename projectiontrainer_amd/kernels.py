@@ -141,6 +141,59 @@ def cross_entropy_(logits, targets, gscale):
     return row_loss
 
 
+def gemm_row_stats(A, B, C, stats, *, M=None, N=None, K=None, ldc=None, ld_stats=None):
+    """The lm_head GEMM with its softmax statistics (ptk_gemm_row_stats): C (bf16, row stride ldc) = A . B^T and, per
+    row and 64-column chunk k, (max, sum exp(x - max)) of the stored bf16 logits at stats[r, 2k : 2k + 2] (f32, row
+    stride ld_stats).  Runs under the current ptk_gemm_force_small_tiles mode.  Returns (C, stats)."""
+    _require_cuda(A, B, C, stats)
+    d = L.GemmDesc()
+    d.A, d.B, d.C = ptr(A), ptr(B), ptr(C)
+    d.M = A.shape[-2] if M is None else M
+    d.N = B.shape[-2] if N is None else N
+    d.K = A.shape[-1] if K is None else K
+    d.lda, d.ldb = A.stride(-2), B.stride(-2)
+    d.ldc = C.stride(-2) if ldc is None else ldc
+    d.batch, d.batch_inner = 1, 1
+    d.alpha, d.act, d.out = 1.0, L.ACT_NONE, L.OUT_BF16
+    check(L.lib().ptk_gemm_row_stats(d, ptr(stats), stats.stride(-2) if ld_stats is None else ld_stats,
+                                     L.stream_ptr(A.device)), "ptk_gemm_row_stats")
+    return C, stats
+
+
+def cross_entropy_stats_(logits, stats, targets, gscale, *, vocab=None, ld_stats=None):
+    """cross_entropy_ from the statistics gemm_row_stats wrote (ptk_cross_entropy_stats): in place on bf16 logits
+    [R, >= vocab] (row stride logits.stride(0)); returns per-row loss."""
+    _require_cuda(logits, stats, targets, gscale)
+    R = logits.shape[0]
+    V = logits.shape[1] if vocab is None else vocab
+    row_loss = torch.empty(R, dtype=torch.float32, device=logits.device)
+    check(L.lib().ptk_cross_entropy_stats(ptr(logits), logits.stride(0), R, V, ptr(stats),
+                                          stats.stride(0) if ld_stats is None else ld_stats, ptr(targets),
+                                          ptr(row_loss), ptr(gscale), L.stream_ptr(logits.device)),
+          "cross_entropy_stats")
+    return row_loss
+
+
+def count_valid(labels, loss_scale=1.0):
+    """(gscale [1], count [1]) f32 of int64 labels (ptk_count_valid): count of labels != -100, gscale = loss_scale /
+    count (0 when nothing is valid)."""
+    _require_cuda(labels)
+    gscale = torch.empty(1, dtype=torch.float32, device=labels.device)
+    count = torch.empty(1, dtype=torch.float32, device=labels.device)
+    check(L.lib().ptk_count_valid(ptr(labels), labels.numel(), float(loss_scale), ptr(gscale), ptr(count),
+                                  L.stream_ptr(labels.device)), "count_valid")
+    return gscale, count
+
+
+def loss_reduce(row_loss, count):
+    """loss [1] f32 = sum(row_loss) / count[0] (ptk_loss_reduce; NaN when count[0] is 0)."""
+    _require_cuda(row_loss, count)
+    loss = torch.empty(1, dtype=torch.float32, device=row_loss.device)
+    check(L.lib().ptk_loss_reduce(ptr(row_loss), row_loss.numel(), ptr(count), ptr(loss),
+                                  L.stream_ptr(row_loss.device)), "loss_reduce")
+    return loss
+
+
 def transpose_rows(x, rows, rows_pad, map_g=0, map_gs=0, map_off=0, ld_out=None):
     """Stage-2 weight-grad operand transpose (ptk_transpose_rows_bf16): out[c][r] = x[map(r)][c] for r < rows,
     0 up to rows_pad; map(r) = (r // g) * gs + r % g + off (g = 0: r + off).  x: 2-D bf16, row stride x.stride(0)."""
