@@ -48,7 +48,42 @@ enum { PTK_OUT_BF16 = 0, PTK_OUT_F32 = 1, PTK_OUT_F32_BF16ROUND = 2 };
  * K-contiguous), K % 64 == 0.  Replaces nn.Linear / torch.matmul / the
  * attention contractions (TF gemma3 :352-382, siglip :280-303,
  * Stage1/projectors.py:17-19).  Epilogue order: +bias[c], +rowadd[r % period],
- * activation, +resid (at the remapped row), store. */
+ * activation, +resid (at the remapped row), store.
+ *
+ * The contract every kernel family implements (tests/gemm_ref.py restates it in fp64), for output row r < M and
+ * column c < N:
+ *   1. v = alpha * sum_k A[amap(r)][k] * B[c][k]   (fp32 accumulation; amap must map every row, amap.skip == 0)
+ *   2. v += bias[c]
+ *   3. v = bf16(v) if bf16_linear
+ *   4. v += rowadd[(r % rowadd_period) * ld_rowadd + c]
+ *   5. GELU_TANH / GELU_ERF / GEGLU: v = bf16(v), the pre-activation; GELU_TANH / GELU_ERF store it to
+ *      aux[r * ld_aux + c], at the UNMAPPED row r (GELU_TANH: only with ld_aux == ldc and an identity cmap)
+ *   6. the activation.  GELU_ERF_BWD: v = bf16(v) * gelu_erf'(aux_in[r * ld_aux_in + c]), the UNMAPPED row.
+ *      GEGLU (N % 32 == 0): columns [32q, 32q + 16) are gate g, [32q + 16, 32q + 32) up u of output columns
+ *      [16q, 16q + 16); a = bf16(gelu_tanh(g)) -> aux, b = bf16(gelu_tanh'(g) * u) -> aux2, both at
+ *      [r * ld_aux + column] of the unmapped row, h = bf16(a * u) -> C [.., N / 2].  GEGLU_BWD (N % 16 == 0): dh =
+ *      bf16(v); dg = bf16(dh * aux_in2[r][c]) -> C column (c / 16) * 32 + c % 16, du = bf16(dh * aux_in[r][c]) 16
+ *      columns on: C is [.., 2 N].  Both read aux_in / aux_in2 at r * ld_aux_in of the unmapped row
+ *   7. cr = cmap(r); nothing of C is written when cr < 0 (a dropped row, or g == 0 with r + off < 0).  Otherwise
+ *      v += resid[cr * ld_resid + c] + resid16[cr * ld_resid16 + c]: both at the MAPPED row (either may be C itself)
+ *   8. C[cr * ldc + c] = bf16(v) (PTK_OUT_BF16), v (PTK_OUT_F32) or (float)bf16(v) (PTK_OUT_F32_BF16ROUND).
+ * Nothing else is written: not rows >= M, columns >= the output width, the padding of a leading dimension or a
+ * dropped row; nothing is read of A rows outside amap's image, B rows >= N, columns >= K, or the side inputs'
+ * padding.
+ *
+ * Accepted ranges; anything else is refused with an error before any device call, never run approximately:
+ *   K % 64 == 0, K > 0; lda % 8 == 0, ldb % 8 == 0, A and B 16-byte aligned; A, B, C not NULL;
+ *   (act, out): PTK_ACT_NONE with every PTK_OUT_*, every other activation with PTK_OUT_BF16;
+ *   rowadd: rowadd_period > 0;
+ *   ldc, ld_resid, ld_resid16, ld_rowadd, ld_aux, ld_aux_in of the plain and GELU epilogues: any value (the kernels
+ *     fall back to narrower accesses; the persistent kernels take multiples of 8 / 4 and leave the rest to the
+ *     128x128 and 256x256 ones);
+ *   PTK_ACT_GELU_TANH with aux: ld_aux == ldc, cmap.g == 0, cmap.off == 0;
+ *   PTK_ACT_GELU_ERF_BWD: aux_in not NULL;
+ *   PTK_ACT_GEGLU: N % 32 == 0, ldc % 4 == 0, ld_aux % 4 == 0 when aux or aux2 is set (8-byte accesses);
+ *   PTK_ACT_GEGLU_BWD: aux_in and aux_in2 not NULL, N % 16 == 0, ldc % 4 == 0, ld_aux_in % 4 == 0;
+ *   PTK_ACT_GEGLU / PTK_ACT_GEGLU_BWD: no bias, rowadd, resid, resid16 or bf16_linear (their epilogues read none).
+ * M <= 0 or N <= 0 launches nothing and returns 0; batch <= 0 and batch_inner <= 0 are taken as 1. */
 typedef struct {
   const void* A;
   const void* B;

@@ -67,6 +67,8 @@ const char* ptk_last_error(void) { return g_err; }
 int ptk_gemm(const ptk_gemm_desc* d, void* stream) {
   if (!d) return set_error("ptk_gemm: null desc");
   if (d->act == PTK_ACT_GEGLU && (d->N % 32)) return set_error("ptk_gemm: GEGLU needs N %% 32 == 0");
+  if (d->rowadd && d->rowadd_period <= 0)   // (to_args would make it 1)
+    return set_error("ptk_gemm: rowadd_period %d must be positive", d->rowadd_period);
   return launch_gemm(to_args(d), d->act, d->out, d->batch > 0 ? d->batch : 1, ST);
 }
 

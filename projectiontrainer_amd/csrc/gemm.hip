@@ -813,6 +813,34 @@ static int row_stats_check(const GemmArgs& a, int act, int out, int batch) {
   return 0;
 }
 
+// The epilogues' own assumptions (include/ptk.h states them next to ptk_gemm_desc): a descriptor is honoured bit
+// for bit or refused here, before any device call.  The plain / GELU epilogues fall back to 4-byte and scalar
+// accesses (vec_ok), so they take any leading dimension; the GEGLU pairs have no scalar form (their narrowest
+// access is 8 bytes: geglu_vec4, geglu_bwd_vec4), read no additive input and drop the columns of a partial
+// 32- / 16-column interleave group; the backward epilogues dereference their saved inputs unconditionally
+static int epilogue_check(const GemmArgs& a, int act) {
+  if (!a.A || !a.B || !a.C) return set_error("gemm: A, B and C must not be NULL");
+  if (a.amap.skip != 0) return set_error("gemm: amap.skip %d (A's row map must map every row)", a.amap.skip);
+  if (a.rowadd && a.rowadd_period <= 0) return set_error("gemm: rowadd_period %d must be positive", a.rowadd_period);
+  if (act == ACT_GELU_ERF_BWD && !a.aux_in) return set_error("gemm: the GELU-erf backward reads aux_in (NULL)");
+  if (act == ACT_GEGLU || act == ACT_GEGLU_BWD) {
+    const char* nm = act == ACT_GEGLU ? "GEGLU" : "GEGLU backward";
+    if (a.bias || a.rowadd || a.resid || a.resid16 || a.bf16_linear)
+      return set_error("gemm: the %s epilogue takes no bias / rowadd / resid / resid16 / bf16_linear", nm);
+    if (a.ldc % 4) return set_error("gemm: %s needs ldc %ld %% 4 == 0 (8-byte stores)", nm, a.ldc);
+  }
+  if (act == ACT_GEGLU) {
+    if (a.N % 32) return set_error("gemm: GEGLU needs N %d %% 32 == 0 (16 | 16 interleaved gate | up columns)", a.N);
+    if ((a.aux || a.aux2) && a.ld_aux % 4) return set_error("gemm: GEGLU needs ld_aux %ld %% 4 == 0 (8-byte stores)", a.ld_aux);
+  }
+  if (act == ACT_GEGLU_BWD) {
+    if (!a.aux_in || !a.aux_in2) return set_error("gemm: the GEGLU backward reads aux_in and aux_in2 (NULL)");
+    if (a.N % 16) return set_error("gemm: GEGLU backward needs N %d %% 16 == 0 (16 | 16 interleaved dg | du columns)", a.N);
+    if (a.ld_aux_in % 4) return set_error("gemm: GEGLU backward needs ld_aux_in %ld %% 4 == 0 (8-byte loads)", a.ld_aux_in);
+  }
+  return 0;
+}
+
 // plan (gemm_plan.cpp: the shape rule) -> launch
 int launch_gemm(const GemmArgs& a, int act, int out, int batch, hipStream_t st, const GemmPlan* planned) {
   if (a.M <= 0 || a.N <= 0 || batch <= 0) return 0;
@@ -827,6 +855,7 @@ int launch_gemm(const GemmArgs& a, int act, int out, int batch, hipStream_t st, 
   if (act == ACT_GELU_TANH && a.aux && (a.ld_aux != a.ldc || a.cmap.g != 0 || a.cmap.off != 0))
     return set_error("gemm: a GELU-tanh pre-activation output needs ld_aux == ldc and an identity C row map");
   if (a.row_stats && row_stats_check(a, act, out, batch)) return -1;
+  if (epilogue_check(a, act)) return -1;
   const GemmPlan plan = planned ? *planned : gemm_plan(a, act, out, batch, gemm_plan_env());
   // k-step-tiled activations are the operands' contract: no family but the one with the variant may run them
   if (a.a_kt && !a_ktiled_ok(a, plan, act, out, batch, lean_epilogue_enabled()))

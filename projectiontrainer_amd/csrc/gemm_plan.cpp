@@ -44,7 +44,8 @@ double w4_round_fill(long M, long N, int ncu) {
 // the lean bf16 epilogue (gemm_persist.h w4_epilogue_lean) applies: ACT_NONE / ACT_GELU_TANH into bf16 with at most
 // a bias, the bf16-linear rounding and a bf16 residual (row-aligned with C, 16-B rows); a C row map that is an
 // offset (cmap.g == 0, or a group map without skipped rows whose group stride equals its size: the identity
-// plus cmap.off); whole 64-column wave ranges; C's extent (rows cmap.off .. M + cmap.off) below 2^31 bytes.
+// plus cmap.off); whole 64-column wave ranges (the 4-wave kernel, whose waves hold 128 columns, asks for N % 128
+// itself: launch_gemm_w4); C's extent (rows cmap.off .. M + cmap.off) below 2^31 bytes.
 // c_bytes = that extent (num_records of the store resource: rows past M are dropped).  lean_epi false
 // (PTK_LEAN_EPI=0 in A/B builds, PTK_AB) keeps the general epilogue (bit-identical either way)
 // the lean GEGLU-backward epilogue (w4_epilogue_lean_glu): the saved g, u inputs with 16-B rows, no other epilogue

@@ -318,7 +318,15 @@ int launch_gemm_w4(const GemmArgs& a, int act, int out, hipStream_t st, int max_
   const uint32_t ab = (uint32_t)std::min<double>((double)arows * a.lda * 2, 2147483000.0);
   const uint32_t bb = (uint32_t)std::min<double>((double)a.N * a.ldb * 2, 2147483000.0);
   uint32_t cb = 0;
-  const bool lean = lean_epilogue_ok(a, act, out, cb, lean_epilogue_enabled());
+  // a wave of this kernel holds 128 columns (two 64-column lines) and w4_epilogue_lean stores both lines of a wave
+  // whose range starts inside N: with N % 128 == 64 the last wave's second line would land in the next row's first
+  // 64 columns (the store resource only ends at C's last byte), so the plain lean epilogue needs whole 128-column
+  // ranges here (the 8-wave kernel's waves hold 64: N % 64 suffices there; lean_glu_ok asks for N % 128 itself).
+  // Its bias loads ran past N the same way.  A shape with N % 128 == 64 takes the general epilogue instead (masking
+  // the second line in the kernel would keep the lean one; its cost on such shapes is not measured, and none of the
+  // model's 4-wave shapes is one: the benchmarked step is unchanged)
+  const bool lean = lean_epilogue_ok(a, act, out, cb, lean_epilogue_enabled()) &&
+                    (act == ACT_GEGLU_BWD || a.N % 128 == 0);
   if (a.c_kt || a.aux_kt || a.aux_in_kt) {   // (launch_gemm checked c_ktiled_ok; a direct caller must have too)
     if (!a.c_kt || !a.B_kt || !((act == ACT_GEGLU && !a.aux_in_kt) || (act == ACT_GEGLU_BWD && lean && !a.aux_kt)))
       return set_error("gemm_w4: no k-step-tiled-output variant for this launch");
