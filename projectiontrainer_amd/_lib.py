@@ -400,3 +400,14 @@ def stage_timers_read(reset=False):
 def stream_ptr(device=None) -> int:
     import torch
     return torch.cuda.current_stream(device).cuda_stream
+
+
+def grow(owner, attr, nbytes, device):
+    """The grow-only byte workspace kept as `owner.<attr>` (unset or None: none yet): returned as it is when it
+    holds `nbytes`, else released FIRST and then reallocated, so the peak never holds both.  It takes the
+    attribute, not the tensor: the owner's reference is what keeps the old buffer alive."""
+    import torch
+    if getattr(owner, attr, None) is None or getattr(owner, attr).numel() < nbytes:
+        setattr(owner, attr, None)
+        setattr(owner, attr, torch.empty(nbytes, dtype=torch.uint8, device=device))
+    return getattr(owner, attr)

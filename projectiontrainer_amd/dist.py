@@ -42,6 +42,8 @@ class DistState:
         return self.process_index == 0
 
     def all_reduce_sum_(self, t):
+        """The trainer's fp32 metric sums (loss totals, counts) over the default group; a no-op on one process.
+        The bf16 grad-store exchange is the module-level all_reduce_bf16_sum_."""
         if self.num_processes > 1:
             dist.all_reduce(t, op=dist.ReduceOp.SUM)
         return t
@@ -162,6 +164,44 @@ def allreduce_grads_chunked_(flat_grad, chunks, world: int, group=None):
         for off, n in chunks:
             dist.all_reduce(flat_grad[off:off + n], op=dist.ReduceOp.SUM, group=group)
     return 1.0 / world
+
+
+# Stage 2's exchange of its flat bf16 stores (ZeRO-1 for the LLM, one all-reduce for the replicated modules).  Each
+# takes the process group and has a gloo path for CPU runs; none is DistState.all_reduce_sum_ (fp32 metrics).
+def reduce_scatter_(out_shard, flat, world, rank, group=None):
+    """Sum of `flat` over ranks, this rank's contiguous shard into out_shard (RCCL reduce-scatter; gloo
+    has none: all-reduce and slice)."""
+    if dist.get_backend(group) == "gloo":
+        t = flat.float()            # gloo has no bf16 sum: fp32 sum of the bf16 values, one rounding
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+        n = out_shard.numel()
+        out_shard.copy_(t[rank * n:(rank + 1) * n])
+    else:
+        dist.reduce_scatter_tensor(out_shard, flat, op=dist.ReduceOp.SUM, group=group)
+    return out_shard
+
+
+def all_reduce_bf16_sum_(t, group=None):
+    """Sum of the bf16 tensor `t` (a whole replicated grad store) over the ranks of `group`, in place: the same
+    bits on every rank.  Not DistState.all_reduce_sum_, which sums fp32 metric scalars over the default group."""
+    if dist.get_backend(group) == "gloo":
+        f = t.float()               # gloo has no bf16 sum: fp32 sum of the bf16 values, one rounding
+        dist.all_reduce(f, op=dist.ReduceOp.SUM, group=group)
+        t.copy_(f)
+    else:
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    return t
+
+
+def all_gather_(flat, shard, world, group=None):
+    """Every rank's `shard` into `flat`, in rank order (the updated ZeRO-1 parameter shards)."""
+    if dist.get_backend(group) == "gloo":
+        parts = [torch.empty(shard.shape, dtype=torch.float32, device=shard.device) for _ in range(world)]
+        dist.all_gather(parts, shard.float(), group=group)     # bf16 -> fp32 -> bf16 is exact
+        flat.copy_(torch.cat(parts))
+    else:
+        dist.all_gather_into_tensor(flat, shard, group=group)
+    return flat
 
 
 class RcclComm:

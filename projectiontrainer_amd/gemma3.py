@@ -221,10 +221,7 @@ class Gemma3CausalLM:
 
     def workspace(self, batch, text_len, seq_pad):
         n = L.lib().ptk_gemma3_workspace_bytes(self.c_cfg, batch, text_len, seq_pad)
-        if self._ws is None or self._ws.numel() < n:
-            self._ws = None
-            self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return L.grow(self, "_ws", n, self.device)
 
     def loss_and_input_grad(self, x, dx, token_ids, labels, num_vision, loss_scale, loss, pad_token_id=None):
         """x: f32 [B*Spad, H] LLM input rows (vision rows filled by the caller),
@@ -291,9 +288,7 @@ class Gemma3CausalLM:
                                  int(seed) & ((1 << 64) - 1), eos, pad, stride, float(top_p))
         ws_fn = "ptk_gemma3_generate" + ("" if penalty == 1.0 else "_penalized") + "_workspace_bytes"
         n = getattr(L.lib(), ws_fn)(self.c_cfg, B, P, max_new_tokens)
-        if getattr(self, "_gen_ws", None) is None or self._gen_ws.numel() < n:
-            self._gen_ws = None
-            self._gen_ws = torch.empty(n, dtype=torch.uint8, device=self.device)
+        L.grow(self, "_gen_ws", n, self.device)
         out = torch.empty((B, max_new_tokens), dtype=torch.int64, device=self.device)
         logits = (torch.empty((max_new_tokens, B, self.cfg.vocab_size), dtype=torch.bfloat16, device=self.device)
                   if return_logits else None)
@@ -330,9 +325,7 @@ class Gemma3CausalLM:
             raise L.PtkError(f"decode: inputs_embeds width {H} != hidden {self.cfg.hidden_size}")
         self._dec = L.Gemma3DecodeC(B * repeat, P, max_new_tokens, repeat, P)
         n = L.lib().ptk_gemma3_decode_workspace_bytes(self.c_cfg, self._dec)
-        if getattr(self, "_dec_ws", None) is None or self._dec_ws.numel() < n:
-            self._dec_ws = None
-            self._dec_ws = torch.empty(n, dtype=torch.uint8, device=self.device)
+        L.grow(self, "_dec_ws", n, self.device)
         mask = None
         if attention_mask is not None:
             mask = attention_mask.to(device=self.device, dtype=torch.int32).contiguous()
@@ -377,8 +370,7 @@ class Gemma3CausalLM:
         penalised = penalty != 1.0 and n_hist > 0
         ws_fn = "ptk_beam_candidates_penalized_workspace_bytes" if penalised else "ptk_beam_candidates_workspace_bytes"
         n = getattr(L.lib(), ws_fn)(B, beams, n_cand)
-        if getattr(self, "_bc_ws", None) is None or self._bc_ws.numel() < n:
-            self._bc_ws = torch.empty(n, dtype=torch.uint8, device=self.device)
+        L.grow(self, "_bc_ws", n, self.device)
         if penalised:
             hist = history.to(device=self.device, dtype=torch.int64)
             if hist.dim() != 2 or hist.shape[0] != rows or hist.stride(1) != 1:   # (rows of a wider buffer pass as is)

@@ -164,9 +164,7 @@ class _ProjectorFn(torch.autograd.Function):
         mod = ctx.mod
         dy = gout.reshape(-1, mod.llm_dim).to(torch.bfloat16).contiguous()
         # workspace and grad scratch kept on the module across calls (grown when a larger batch comes)
-        nb = mod.workspace_bytes(xb.shape[0])
-        if getattr(mod, "_bwd_ws", None) is None or mod._bwd_ws.numel() < nb:
-            mod._bwd_ws = torch.empty(nb, dtype=torch.uint8, device=xb.device)
+        L.grow(mod, "_bwd_ws", mod.workspace_bytes(xb.shape[0]), xb.device)
         if getattr(mod, "_grad_tmp", None) is None:
             mod._grad_tmp = torch.empty_like(mod.flat_grad)
         g = [mod._grad_tmp[o:o + k] for o, k, _ in mod._views]

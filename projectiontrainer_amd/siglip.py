@@ -107,9 +107,7 @@ class SiglipVisionTower:
 
     def workspace(self, batch):
         n = L.lib().ptk_siglip_workspace_bytes(self.c_cfg, batch)
-        if self._ws is None or self._ws.numel() < n:
-            self._ws = torch.empty(n, dtype=torch.uint8, device=self.device)
-        return self._ws
+        return L.grow(self, "_ws", n, self.device)
 
     def forward_into(self, pixels_bf16, out):
         """pixels bf16 [B,C,H,W] -> out bf16 [B*N, D] (last_hidden_state, all patches)."""

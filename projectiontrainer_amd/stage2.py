@@ -23,36 +23,35 @@ and vision encoder frozen; no QLoRA):
                                          all-gather of the updated parameters
   lr_scheduler.step() x num_processes    host-side cosine-with-warmup lambda
 
-Parameter store: every Gemma3 parameter lives in ONE flat bf16 buffer in the kernel layouts (q|k|v fused,
-gate/up interleaved per 16 rows), the layer tensors being views of it; the grads in a second buffer of the
-same layout.  Under `--mixed_precision bf16` the reference loads the LLM in bf16
-(train_vqa_stage2.py:141-147,180-187), so its parameters, grads and AdamW moments are bf16 tensors: the
-store keeps exactly that (no fp32 master copy), and the optimizer rounds every tensor op to bf16 as
-torch's AdamW does on bf16 parameters.  The transposed copies the dX GEMMs read and the fp32 copies of the
-norm weights the norm kernels read are refreshed after each optimizer step.
+Parameter stores: under `--mixed_precision bf16` the reference holds every trained module in bf16 (the LLM and
+the tower loaded so, train_vqa_stage2.py:141-153,180-187; the projector cast, :274), so parameters, grads and
+AdamW moments are bf16 tensors with no fp32 master, and the optimizer rounds every tensor op to bf16 as torch's
+AdamW does on bf16 parameters.  Each trained module keeps exactly that in one `FlatStore` (flat_store.py) in the
+kernel layouts, the module's tensors rebound onto views of it: `Gemma3TrainState` (q|k|v fused, gate/up
+interleaved per 16 rows), `ProjectorTrainState` ([W1 | b1 | W2 | b2]) and `SiglipTrainState` (q|k|v rows fused,
+the conv weight flattened).  The derived copies the kernels read (transposes for the dX GEMMs, the fp32 mirror of
+norm weights / biases / positions) are refreshed after each optimizer step.
+
+The optimizer step clips each trained module on its own norm (:437-439) and applies ptk_adamw_bf16 to each with
+the shared LR / step count.  The LLM's store is ZeRO-1 sharded, its moments being the engine's shards.  The
+projector's and the tower's are replicated and own their moments: at world > 1 their grads are summed by one
+all-reduce (44 MB of bf16 for the projector's 22 M parameters, ~0.6 GB for the L/16 tower, next to the LLM's 2 GB
+reduce-scatter; the tower's cost is unmeasured), scaled by 1 / world before the sum of squares, and every rank
+takes the same deterministic step, so the replicas stay bit-identical without a parameter exchange.
 
 Trainable projector (Stage2/trainer.py:214-223 collects its parameters, :336-337 runs it with grad; modes B, C).
-`train_vqa_stage2.py:274` casts it to bf16 under `--mixed_precision bf16`, so its parameters, grads and moments are
-bf16 too: `ProjectorTrainState` holds [W1 | b1 | W2 | b2] in one flat bf16 store (a second one for the grads, two
-for the moments), rounded once from the module it is given.  Per micro-batch, after the Gemma3 call:
+Per micro-batch, after the Gemma3 call:
   dy = bf16(dx[vision rows]), patch 0's row zero          ptk_gather_vision_grad
   db2, dW2, dA = bf16((dy W2) gelu'(a)), db1, dW1         ptk_projector_bwd_bf16: each G rounded once to bf16 and
                                                           accumulated as autograd does, bf16(grad + bf16(G))
 The forward is the frozen projector's (ptk_projector_fwd, bf16 GEMMs, output rounded to bf16), reading W1 / W2 from
-the store; W2^T and the fp32 biases it takes are refreshed after each step.  The optimizer step clips each module
-on its own norm (:437-439) and applies ptk_adamw_bf16 to both with the shared LR / step count.  The projector
-store is replicated, not sharded: at world > 1 its grads are summed by one all-reduce (44 MB of bf16 at 22 M
-parameters, next to the LLM's 2 GB reduce-scatter), scaled by 1 / world before the sum of squares, and every rank
-takes the same deterministic step, so the replicas stay bit-identical without a parameter exchange.
-Mode C builds no Gemma3TrainState: the LLM keeps the k-step-tiled frozen weights it was built with and runs
-ptk_gemma3_loss_fwd_bwd (loss and dX only, label_offset = the question length).
+the store.  Mode C builds no Gemma3TrainState: the LLM keeps the k-step-tiled frozen weights it was built with and
+runs ptk_gemma3_loss_fwd_bwd (loss and dX only, label_offset = the question length).
 
 Trainable vision tower (train_vision=True; the reference's --unfreeze_vision_encoder / first-epoch fine-tune,
 Stage2/trainer.py:214-237,267-289, whose two flags exclude each other in its run script, so the tower never
 trains there and no recorded step exists to match: the yardstick is torch autograd through
-oracle.stage1_ref.siglip_vision_forward).  The reference loads the tower in bf16 under --mixed_precision bf16
-(train_vqa_stage2.py:141-153): `SiglipTrainState` holds every tower parameter in one flat bf16 store (grads and
-two moments in three more), rebinding the tower's tensors.  Per micro-batch:
+oracle.stage1_ref.siglip_vision_forward).  Per micro-batch:
   SigLIP fwd keeping activations                           ptk_siglip_train_fwd (bit-identical to ptk_siglip_fwd)
   ... projector fwd, Gemma3 fwd / loss / bwd as above ...
   dy = bf16(dx[vision rows]), patch 0's row zero           ptk_gather_vision_grad
@@ -60,28 +59,26 @@ two moments in three more), rebinding the tower's tensors.  Per micro-batch:
                                                            grads only when the projector is trained)
   every tower grad, accumulated bf16(grad + bf16(G))       ptk_siglip_bwd; d(vis) is d(last_hidden_state), its
                                                            patch-0 rows zero ([:, 1:] drops that patch)
-With train_vision=False none of this runs and nothing the engine computes changes.  optimizer_step clips the tower
-on its own norm and applies ptk_adamw_bf16 with the shared LR / step count; the store is replicated like the
-projector's (one all-reduce of ~0.6 GB of bf16 grads for L/16, scaled by 1 / world before the sum of squares, the
-same deterministic step on every rank; its cost next to the LLM's ZeRO-1 exchange is unmeasured).
+With train_vision=False none of this runs and nothing the engine computes changes.
 set_vision_trainable(False) freezes the tower again (frozen forward, no tower backward, no tower step) while
 keeping its store, moments and the step count: the hook for a first-epoch-only schedule.
 """
 from __future__ import annotations
-
-import math
 
 import torch
 import torch.distributed as dist
 
 from . import _lib as L
 from . import kernels as K
+from .dist import all_gather_, all_reduce_bf16_sum_, reduce_scatter_
+from .flat_store import FlatStore
 from .gemma3 import Gemma3CausalLM
 from .projectors import MLPProjector
 from .siglip import SiglipVisionTower
 from .stage1 import cosine_lambda
 
 LAYER_KEYS = ("wqkv", "wo", "wgu", "wd", "ln_in", "ln_post_attn", "ln_pre_ff", "ln_post_ff", "q_norm", "k_norm")
+LAYER_MATS = ("wqkv", "wo", "wgu", "wd")
 NORM_KEYS = ("ln_in", "ln_post_attn", "ln_pre_ff", "ln_post_ff", "q_norm", "k_norm")
 HF_NORM = {"ln_in": "input_layernorm", "ln_post_attn": "post_attention_layernorm",
            "ln_pre_ff": "pre_feedforward_layernorm", "ln_post_ff": "post_feedforward_layernorm",
@@ -96,34 +93,20 @@ def deinterleave_gate_up(wgu):
     return v[:, 0].reshape(I2 // 2, H), v[:, 1].reshape(I2 // 2, H)
 
 
-class Gemma3TrainState:
-    """Flat bf16 parameter / grad store of an unfrozen Gemma3CausalLM (rebinds the model's tensors)."""
-
-    ALIGN = 64   # elements: every segment 128-B aligned
+class Gemma3TrainState(FlatStore):
+    """Flat bf16 parameter / grad store of an unfrozen Gemma3CausalLM (rebinds the model's tensors).  The AdamW
+    moments are ZeRO-1 shards and live in the engine."""
 
     def __init__(self, llm: Gemma3CausalLM, world_size: int = 1):
         self.llm, self.world = llm, world_size
-        cfg, dev = llm.cfg, llm.device
-        # matrices first, then every norm weight in one contiguous region (its fp32 mirror, which the norm
-        # kernels read, is refreshed with one copy)
-        segs = [("embed", tuple(llm.embed.shape))]
+        # matrices first, then every norm weight in the mirrored region (the norm kernels read them in fp32)
+        segs = [("embed", llm.embed.shape)]
         for i, lay in enumerate(llm.layers):
-            segs += [(f"{i}.{k}", tuple(lay[k].shape)) for k in ("wqkv", "wo", "wgu", "wd")]
-        norm_segs = [("final_norm", (cfg.hidden_size,))]
+            segs += [(f"{i}.{k}", lay[k].shape) for k in LAYER_MATS]
+        norm_segs = [("final_norm", (llm.cfg.hidden_size,))]
         for i, lay in enumerate(llm.layers):
-            norm_segs += [(f"{i}.{k}", tuple(lay[k].shape)) for k in NORM_KEYS]
-        off, self.offsets = 0, {}
-        for j, (name, shape) in enumerate(segs + norm_segs):
-            if j == len(segs):
-                self.norm_lo = off
-            self.offsets[name] = (off, shape)
-            n = math.prod(shape)
-            off += (n + self.ALIGN - 1) // self.ALIGN * self.ALIGN
-        self.norm_hi = off
-        unit = self.ALIGN * world_size
-        self.numel = (off + unit - 1) // unit * unit          # equal ZeRO shards
-        self.flat = torch.zeros(self.numel, dtype=torch.bfloat16, device=dev)
-        self.grad = torch.zeros(self.numel, dtype=torch.bfloat16, device=dev)
+            norm_segs += [(f"{i}.{k}", lay[k].shape) for k in NORM_KEYS]
+        super().__init__(segs, norm_segs, device=llm.device, pad_to=64 * world_size)   # equal ZeRO shards
         # copy the current weights in (bf16 matrices as they are; norm weights rounded to bf16, as the
         # reference's bf16-loaded model holds them), then rebind the model onto views of the store
         self.view("embed").copy_(llm.embed)
@@ -132,25 +115,16 @@ class Gemma3TrainState:
             for k in LAYER_KEYS:
                 self.view(f"{i}.{k}").copy_(lay[k])
         llm.embed = self.view("embed")
-        self.norm32 = torch.zeros(self.norm_hi - self.norm_lo, dtype=torch.float32, device=dev)
-        n32 = lambda name: self.norm32[self.offsets[name][0] - self.norm_lo:][:math.prod(self.offsets[name][1])]
-        llm.final_norm = n32("final_norm")
+        llm.final_norm = self.mirror_view("final_norm")
         for i, lay in enumerate(llm.layers):
-            for k in ("wqkv", "wo", "wgu", "wd"):
+            for k in LAYER_MATS:
                 lay[k] = self.view(f"{i}.{k}")
             for k in NORM_KEYS:
-                lay[k] = n32(f"{i}.{k}").view(self.offsets[f"{i}.{k}"][1])
+                lay[k] = self.mirror_view(f"{i}.{k}")
         llm.drop_ktiled()
         self.refresh()
         llm._build_c()
         self._build_grads_c()
-
-    def view(self, name, buf=None):
-        off, shape = self.offsets[name]
-        return (self.flat if buf is None else buf)[off:off + math.prod(shape)].view(shape)
-
-    def grad_view(self, name):
-        return self.view(name, self.grad)
 
     def _build_grads_c(self):
         arr = (L.Gemma3LayerGradsC * len(self.llm.layers))()
@@ -163,14 +137,11 @@ class Gemma3TrainState:
     def refresh(self):
         """Derived copies the kernels read: transposed matrices (dX GEMMs) and fp32 norm weights."""
         llm = self.llm
-        self.norm32.copy_(self.flat[self.norm_lo:self.norm_hi])
+        self.refresh_mirror()
         for lay in llm.layers:
-            for k in ("wqkv", "wo", "wgu", "wd"):
+            for k in LAYER_MATS:
                 K.transpose(lay[k], out=lay[k + "_t"])
         K.transpose(llm.embed, out=llm.embed_t)
-
-    def zero_grad(self):
-        self.grad.zero_()
 
     def shard(self, rank):
         n = self.numel // self.world
@@ -198,45 +169,26 @@ class Gemma3TrainState:
         return sd
 
 
-class ProjectorTrainState:
-    """Flat bf16 parameter / grad / moment store of a trainable Stage-2 projector.
-
-    Under `--mixed_precision bf16` the reference casts the projector (train_vqa_stage2.py:274), so its parameters,
-    grads and AdamW moments are bf16 tensors: the store holds [W1 | b1 | W2 | b2] (each segment 128-B aligned, the
-    gaps zero) rounded from whatever the module holds, the grads in a second buffer of the same layout, and no
-    fp32 master.  The kernels read W1 and W2 from the store itself; W2^T (the dA GEMM's operand) and the fp32
-    biases ptk_projector_fwd takes are derived copies, refreshed after each optimizer step.  Stage 1's
-    MLPProjector (fp32 masters, `flat` / `flat_grad`) is only read here, never changed."""
-
-    ALIGN = 64   # elements
+class ProjectorTrainState(FlatStore):
+    """Flat bf16 parameter / grad / moment store of a trainable Stage-2 projector: [W1 | b1 | W2 | b2], rounded
+    from whatever the module holds.  The kernels read W1 and W2 from the store itself; W2^T (the dA GEMM's
+    operand) and the fp32 biases ptk_projector_fwd takes are derived copies, refreshed after each optimizer step
+    (the biases sit between the matrices, so they are copied one by one and not through a mirrored region).
+    Stage 1's MLPProjector (fp32 masters, `flat` / `flat_grad`) is only read here, never changed."""
 
     def __init__(self, proj: MLPProjector, device):
         Dv, I, Dl = proj.vision_dim, proj.inter_dim, proj.llm_dim
         self.dims = (Dv, I, Dl)
-        off, self.offsets = 0, {}
-        for name, shape in zip(PROJ_KEYS, ((I, Dv), (I,), (Dl, I), (Dl,))):
-            self.offsets[name] = (off, shape)
-            off += (math.prod(shape) + self.ALIGN - 1) // self.ALIGN * self.ALIGN
-        self.numel = off
-        bf = torch.bfloat16
-        self.flat = torch.zeros(off, dtype=bf, device=device)
-        self.grad = torch.zeros(off, dtype=bf, device=device)
-        self.exp_avg = torch.zeros(off, dtype=bf, device=device)
-        self.exp_avg_sq = torch.zeros(off, dtype=bf, device=device)
+        super().__init__(zip(PROJ_KEYS, ((I, Dv), (I,), (Dl, I), (Dl,))), device=device, moments=True)
         for name, p in zip(PROJ_KEYS, (proj.w1, proj.b1, proj.w2, proj.b2)):
             K.cast_bf16(p.detach().to(device=device, dtype=torch.float32).contiguous(), self.view(name))
-        self.w2t = torch.empty((I, Dl), dtype=bf, device=device)
+        self.w2t = torch.empty((I, Dl), dtype=torch.bfloat16, device=device)
         self.bias32 = torch.zeros(I + Dl, dtype=torch.float32, device=device)
         self.tail = torch.zeros(L.lib().ptk_gemm_tail_scratch_bytes(), dtype=torch.uint8, device=device)
-        self.sumsq = torch.zeros(1, dtype=torch.float32, device=device)
         self.c = L.ProjectorC(Dv, I, Dl, self.view(PROJ_KEYS[0]).data_ptr(), self.bias32.data_ptr(),
                               self.view(PROJ_KEYS[2]).data_ptr(), self.bias32[I:].data_ptr(), self.w2t.data_ptr(),
                               self.tail.data_ptr())
         self.refresh()
-
-    def view(self, name, buf=None):
-        off, shape = self.offsets[name]
-        return (self.flat if buf is None else buf)[off:off + math.prod(shape)].view(shape)
 
     def refresh(self):
         """Derived copies the kernels read: W2^T and the fp32 biases."""
@@ -252,6 +204,7 @@ class ProjectorTrainState:
 
 
 SIGLIP_MATS = ("wqkv", "wo", "w1", "w2")
+SIGLIP_TOP_SMALL = ("patch_b", "pos", "post_w", "post_b")
 SIGLIP_SMALL = ("bqkv", "bo", "b1", "b2", "ln1_w", "ln1_b", "ln2_w", "ln2_b")
 SIGLIP_GRAD_KEYS = ("wqkv", "bqkv", "wo", "bo", "w1", "b1", "w2", "b2", "ln1_w", "ln1_b", "ln2_w", "ln2_b")
 SIGLIP_HF = {"wo": "self_attn.out_proj.weight", "bo": "self_attn.out_proj.bias", "w1": "mlp.fc1.weight",
@@ -259,66 +212,43 @@ SIGLIP_HF = {"wo": "self_attn.out_proj.weight", "bo": "self_attn.out_proj.bias",
              "ln1_b": "layer_norm1.bias", "ln2_w": "layer_norm2.weight", "ln2_b": "layer_norm2.bias"}
 
 
-class SiglipTrainState:
-    """Flat bf16 parameter / grad / moment store of a trained SigLIP tower (rebinds the tower's tensors).
-
-    Under `--mixed_precision bf16` the reference loads the vision tower in bf16 (train_vqa_stage2.py:141-153), so its
-    parameters, grads and AdamW moments are bf16 tensors: every parameter lives in ONE flat bf16 buffer in the
-    kernel layouts (q|k|v rows fused, the conv weight flattened (c, ky, kx)), the matrices first, then the
-    positions, biases and LayerNorm parameters in one contiguous region.  The tower's GEMM weights become views
-    of the store; its fp32 positions / biases / LN parameters, which the forward kernels read, become views of one
-    fp32 mirror of that region, refreshed after each optimizer step (as ProjectorTrainState.refresh does).  The
-    k-step-tiled weight copies are dropped: they are copies of frozen weights.  The grads live in a second
-    buffer of the same layout (ptk_siglip_bwd accumulates into it), the moments in two more."""
-
-    ALIGN = 64   # elements
+class SiglipTrainState(FlatStore):
+    """Flat bf16 parameter / grad / moment store of a trained SigLIP tower (rebinds the tower's tensors): the
+    matrices first (q|k|v rows fused, the conv weight flattened (c, ky, kx)), then the positions, biases and
+    LayerNorm parameters in the mirrored region.  The tower's GEMM weights become views of the store; its fp32
+    positions / biases / LN parameters, which the forward kernels read, become views of the fp32 mirror.  The
+    k-step-tiled weight copies are dropped: they are copies of frozen weights.  ptk_siglip_bwd accumulates into
+    the grad buffer."""
 
     def __init__(self, tower: SiglipVisionTower):
         self.tower = tower
-        dev = tower.device
         nl = len(tower.layers)
-        segs = [("patch_w", tuple(tower.patch_w.shape))]
+        segs = [("patch_w", tower.patch_w.shape)]
         for i, lay in enumerate(tower.layers):
-            segs += [(f"{i}.{k}", tuple(lay[k].shape)) for k in SIGLIP_MATS]
-        small = [(k, tuple(getattr(tower, k).shape)) for k in ("patch_b", "pos", "post_w", "post_b")]
+            segs += [(f"{i}.{k}", lay[k].shape) for k in SIGLIP_MATS]
+        small = [(k, getattr(tower, k).shape) for k in SIGLIP_TOP_SMALL]
         for i, lay in enumerate(tower.layers):
-            small += [(f"{i}.{k}", tuple(lay[k].shape)) for k in SIGLIP_SMALL]
-        off, self.offsets = 0, {}
-        for j, (name, shape) in enumerate(segs + small):
-            if j == len(segs):
-                self.small_lo = off
-            self.offsets[name] = (off, shape)
-            off += (math.prod(shape) + self.ALIGN - 1) // self.ALIGN * self.ALIGN
-        self.small_hi = self.numel = off
-        bf = torch.bfloat16
-        self.flat = torch.zeros(off, dtype=bf, device=dev)
-        self.grad = torch.zeros(off, dtype=bf, device=dev)
-        self.exp_avg = torch.zeros(off, dtype=bf, device=dev)
-        self.exp_avg_sq = torch.zeros(off, dtype=bf, device=dev)
-        self.sumsq = torch.zeros(1, dtype=torch.float32, device=dev)
-        self.small32 = torch.zeros(self.small_hi - self.small_lo, dtype=torch.float32, device=dev)
+            small += [(f"{i}.{k}", lay[k].shape) for k in SIGLIP_SMALL]
+        super().__init__(segs, small, device=tower.device, moments=True)
         # the current weights in (the fp32 ones rounded to bf16, as the reference's bf16-loaded tower holds them),
         # then the tower rebound onto views of the store / of the fp32 mirror
         for name, _ in segs + small:
             self.view(name).copy_(self._tower_tensor(name))
-        s32 = lambda name: self.small32[self.offsets[name][0] - self.small_lo:][:math.prod(self.offsets[name][1])] \
-            .view(self.offsets[name][1])
         tower.patch_w = self.view("patch_w")
-        for k in ("patch_b", "pos", "post_w", "post_b"):
-            setattr(tower, k, s32(k))
+        for k in SIGLIP_TOP_SMALL:
+            setattr(tower, k, self.mirror_view(k))
         for i, lay in enumerate(tower.layers):
             for k in SIGLIP_MATS:
                 lay[k] = self.view(f"{i}.{k}")
             for k in SIGLIP_SMALL:
-                lay[k] = s32(f"{i}.{k}")
+                lay[k] = self.mirror_view(f"{i}.{k}")
         self.refresh()
         tower._build_c(ktiled=False)
         arr = (L.SiglipLayerGradsC * nl)()
         for i in range(nl):
             arr[i] = L.SiglipLayerGradsC(*[self.grad_view(f"{i}.{k}").data_ptr() for k in SIGLIP_GRAD_KEYS])
         self._c_layer_grads = arr
-        self.c_grads = L.SiglipGradsC(*[self.grad_view(k).data_ptr() for k in ("patch_w", "patch_b", "pos", "post_w",
-                                                                                 "post_b")], arr)
+        self.c_grads = L.SiglipGradsC(*[self.grad_view(k).data_ptr() for k in ("patch_w",) + SIGLIP_TOP_SMALL], arr)
         self._ws = None
 
     def _tower_tensor(self, name):
@@ -327,27 +257,14 @@ class SiglipTrainState:
             return self.tower.layers[int(i)][k]
         return getattr(self.tower, name)
 
-    def view(self, name, buf=None):
-        off, shape = self.offsets[name]
-        return (self.flat if buf is None else buf)[off:off + math.prod(shape)].view(shape)
-
-    def grad_view(self, name):
-        return self.view(name, self.grad)
-
     def refresh(self):
         """The fp32 copies the forward kernels read (positions, biases, LN parameters)."""
-        self.small32.copy_(self.flat[self.small_lo:self.small_hi])
+        self.refresh_mirror()
 
     def workspace(self, batch):
         """Saved activations + backward scratch of ptk_siglip_train_fwd / ptk_siglip_bwd at this batch."""
         n = L.lib().ptk_siglip_train_workspace_bytes(self.tower.c_cfg, batch)
-        if self._ws is None or self._ws.numel() < n:
-            self._ws = None
-            self._ws = torch.empty(n, dtype=torch.uint8, device=self.tower.device)
-        return self._ws
-
-    def zero_grad(self):
-        self.grad.zero_()
+        return L.grow(self, "_ws", n, self.tower.device)
 
     def state_dict_hf(self, grads=False):
         """HF SiglipVisionModel names (`vision_model.*`), bf16 tensors on the device: q|k|v split again, the conv
@@ -456,15 +373,9 @@ class Stage2Engine:
             lib = L.lib()
             ws_fn = lib.ptk_projector_bwd_bf16_workspace_bytes if self.vstate is None else \
                 lib.ptk_projector_input_grad_workspace_bytes
-            nb = ws_fn(self._proj_c(), B * N)
-            if getattr(self, "_proj_ws", None) is None or self._proj_ws.numel() < nb:
-                self._proj_ws = None
-                self._proj_ws = torch.empty(nb, dtype=torch.uint8, device=dev)
+            L.grow(self, "_proj_ws", ws_fn(self._proj_c(), B * N), dev)
         ws_bytes = L.lib().ptk_gemma3_train_workspace_bytes if self.train_llm else L.lib().ptk_gemma3_workspace_bytes
-        n = ws_bytes(self.llm.c_cfg, B, T, Sp)
-        if getattr(self, "_ws", None) is None or self._ws.numel() < n:
-            self._ws = None
-            self._ws = torch.empty(n, dtype=torch.uint8, device=dev)
+        L.grow(self, "_ws", ws_bytes(self.llm.c_cfg, B, T, Sp), dev)
         self._shape = (B, T)
 
     def _proj_c(self):
@@ -564,75 +475,59 @@ class Stage2Engine:
         if self.train_llm:
             self._llm_step(lr)
         if self.pstate is not None:
-            self._projector_step(lr)
+            self._replicated_step(self.pstate, self.proj_grad_norm, lr)
         if self.vision_trainable:
-            self._vision_step(lr)
+            self._replicated_step(self.vstate, self.vision_grad_norm, lr)
         self.sched_step += self.world
         self.last_lr = lr       # the LR this optimizer step used (param_groups[0]["lr"] during .step())
         return lr
 
+    def _clip_adamw(self, p, g, exp_avg, exp_avg_sq, n, scale, sumsq, norm_out, lr, sum_over_ranks=False):
+        """g *= scale and its sum of squares into `sumsq` (summed over the ranks' shards when asked), then the
+        clip on that norm (written to `norm_out`) and bf16 AdamW on p, with the engine's shared betas, eps, weight
+        decay, max norm and step count."""
+        stream = L.stream_ptr(self.device)
+        L.check(L.lib().ptk_bf16_grad_scale_sumsq(g.data_ptr(), n, scale, self._partial.data_ptr(),
+                                                  sumsq.data_ptr(), stream), "grad_scale_sumsq")
+        if sum_over_ranks:
+            dist.all_reduce(sumsq, op=dist.ReduceOp.SUM, group=self.pg)
+        b1, b2 = self.betas
+        L.check(L.lib().ptk_adamw_bf16(p.data_ptr(), g.data_ptr(), exp_avg.data_ptr(), exp_avg_sq.data_ptr(), n,
+                                       sumsq.data_ptr(), self.max_norm, lr, b1, b2, self.eps, self.wd,
+                                       self.opt_step, norm_out.data_ptr(), stream), "adamw_bf16")
+
     def _llm_step(self, lr):
-        st, stream = self.state, L.stream_ptr(self.device)
+        """ZeRO-1: reduce-scatter of the grads, clip + AdamW on this rank's shard, all-gather of the parameters."""
+        st = self.state
         lo, n = self.shard_lo, self.shard_n
         if self.zero1:
             reduce_scatter_(self._shard_grad, st.grad, self.world, self.rank, self.pg)
             g, scale = self._shard_grad, 1.0 / self.world
         else:
             g, scale = st.grad, 1.0
-        L.check(L.lib().ptk_bf16_grad_scale_sumsq(g.data_ptr(), n, scale, self._partial.data_ptr(),
-                                                  self.sumsq.data_ptr(), stream), "grad_scale_sumsq")
-        if self.zero1:
-            dist.all_reduce(self.sumsq, op=dist.ReduceOp.SUM, group=self.pg)
-        b1, b2 = self.betas
         p = st.flat[lo:lo + n]
-        L.check(L.lib().ptk_adamw_bf16(p.data_ptr(), g.data_ptr(), self.exp_avg.data_ptr(),
-                                       self.exp_avg_sq.data_ptr(), n, self.sumsq.data_ptr(), self.max_norm, lr, b1,
-                                       b2, self.eps, self.wd, self.opt_step, self.grad_norm.data_ptr(), stream),
-                "adamw_bf16")
+        self._clip_adamw(p, g, self.exp_avg, self.exp_avg_sq, n, scale, self.sumsq, self.grad_norm, lr,
+                         sum_over_ranks=self.zero1)
         if self.zero1:
             self._shard_param.copy_(p)
             all_gather_(st.flat, self._shard_param, self.world, self.pg)
         st.refresh()
         st.zero_grad()
 
-    def _projector_step(self, lr):
-        """The projector's own clip + AdamW on its whole store: at world > 1 the ranks' grads are summed by one
-        all-reduce (every rank receives the same bits), scaled by 1 / world before the sum of squares as the
-        LLM's shards are, and every rank takes the same deterministic step, so the replicas stay bit-identical
-        without a parameter exchange."""
-        ps, stream = self.pstate, L.stream_ptr(self.device)
+    def _replicated_step(self, store, norm_out, lr):
+        """A replicated module's own clip + AdamW on its whole store (the projector, the tower;
+        Stage2/trainer.py:433-439 clips each trained module separately): at world > 1 the ranks' grads are summed
+        by one all-reduce (every rank receives the same bits), scaled by 1 / world before the sum of squares as
+        the LLM's shards are, and every rank takes the same deterministic step, so the replicas stay
+        bit-identical without a parameter exchange."""
         scale = 1.0
         if self.zero1:
-            all_reduce_sum_(ps.grad, self.pg)
+            all_reduce_bf16_sum_(store.grad, self.pg)
             scale = 1.0 / self.world
-        L.check(L.lib().ptk_bf16_grad_scale_sumsq(ps.grad.data_ptr(), ps.numel, scale, self._partial.data_ptr(),
-                                                  ps.sumsq.data_ptr(), stream), "grad_scale_sumsq")
-        b1, b2 = self.betas
-        L.check(L.lib().ptk_adamw_bf16(ps.flat.data_ptr(), ps.grad.data_ptr(), ps.exp_avg.data_ptr(),
-                                       ps.exp_avg_sq.data_ptr(), ps.numel, ps.sumsq.data_ptr(), self.max_norm, lr,
-                                       b1, b2, self.eps, self.wd, self.opt_step, self.proj_grad_norm.data_ptr(),
-                                       stream), "adamw_bf16")
-        ps.refresh()
-        ps.grad.zero_()
-
-    def _vision_step(self, lr):
-        """The tower's own clip + AdamW on its whole store, exactly as _projector_step treats the projector's: one
-        all-reduce of the replicated grads at world > 1, scaled by 1 / world before the sum of squares, the same
-        deterministic step on every rank (Stage2/trainer.py:433-439 clips each trained module separately)."""
-        vs, stream = self.vstate, L.stream_ptr(self.device)
-        scale = 1.0
-        if self.zero1:
-            all_reduce_sum_(vs.grad, self.pg)
-            scale = 1.0 / self.world
-        L.check(L.lib().ptk_bf16_grad_scale_sumsq(vs.grad.data_ptr(), vs.numel, scale, self._partial.data_ptr(),
-                                                  vs.sumsq.data_ptr(), stream), "grad_scale_sumsq")
-        b1, b2 = self.betas
-        L.check(L.lib().ptk_adamw_bf16(vs.flat.data_ptr(), vs.grad.data_ptr(), vs.exp_avg.data_ptr(),
-                                       vs.exp_avg_sq.data_ptr(), vs.numel, vs.sumsq.data_ptr(), self.max_norm, lr,
-                                       b1, b2, self.eps, self.wd, self.opt_step, self.vision_grad_norm.data_ptr(),
-                                       stream), "adamw_bf16")
-        vs.refresh()
-        vs.zero_grad()
+        self._clip_adamw(store.flat, store.grad, store.exp_avg, store.exp_avg_sq, store.numel, scale, store.sumsq,
+                         norm_out, lr)
+        store.refresh()
+        store.zero_grad()
 
     @property
     def scheduler_lr(self):
@@ -648,21 +543,21 @@ class Stage2Engine:
         sd = {"exp_avg": self.exp_avg.cpu(), "exp_avg_sq": self.exp_avg_sq.cpu(), "step": self.opt_step,
               "sched_step": self.sched_step, "shard": (self.shard_lo, self.shard_n), "world": self.world,
               "rank": self.rank, "numel": self._llm_numel}
-        if self.pstate is not None:   # the projector's moments, whole on every rank (its store is replicated)
-            sd.update(proj_exp_avg=self.pstate.exp_avg.cpu(), proj_exp_avg_sq=self.pstate.exp_avg_sq.cpu(),
-                      proj_numel=self.pstate.numel)
-        if self.vstate is not None:   # the tower's moments, whole on every rank too
-            sd.update(vision_exp_avg=self.vstate.exp_avg.cpu(), vision_exp_avg_sq=self.vstate.exp_avg_sq.cpu(),
-                      vision_numel=self.vstate.numel)
+        for key, st in self._replicated():   # their moments, whole on every rank (the stores are replicated)
+            sd.update({f"{key}_exp_avg": st.exp_avg.cpu(), f"{key}_exp_avg_sq": st.exp_avg_sq.cpu(),
+                       f"{key}_numel": st.numel})
         return sd
 
     @property
     def _llm_numel(self):
         return self.state.numel if self.train_llm else 0
 
+    def _replicated(self):
+        """(checkpoint key prefix, store) of the replicated stores this engine was built with."""
+        return [(key, st) for key, st in (("proj", self.pstate), ("vision", self.vstate)) if st is not None]
+
     def load_optimizer_state(self, sd):
-        pn = self.pstate.numel if self.pstate is not None else 0
-        vn = self.vstate.numel if self.vstate is not None else 0
+        pn, vn = (0 if st is None else st.numel for st in (self.pstate, self.vstate))
         if (sd["world"], sd["rank"], sd["numel"], sd.get("proj_numel", 0), sd.get("vision_numel", 0)) != (
                 self.world, self.rank, self._llm_numel, pn, vn):
             raise ValueError(f"optimizer shard of world {sd['world']} rank {sd['rank']} (store {sd['numel']}, "
@@ -671,12 +566,9 @@ class Stage2Engine:
                              f"projector {pn}, vision {vn})")
         self.exp_avg.copy_(sd["exp_avg"])
         self.exp_avg_sq.copy_(sd["exp_avg_sq"])
-        if self.pstate is not None:
-            self.pstate.exp_avg.copy_(sd["proj_exp_avg"])
-            self.pstate.exp_avg_sq.copy_(sd["proj_exp_avg_sq"])
-        if self.vstate is not None:
-            self.vstate.exp_avg.copy_(sd["vision_exp_avg"])
-            self.vstate.exp_avg_sq.copy_(sd["vision_exp_avg_sq"])
+        for key, st in self._replicated():
+            st.exp_avg.copy_(sd[f"{key}_exp_avg"])
+            st.exp_avg_sq.copy_(sd[f"{key}_exp_avg_sq"])
         self.opt_step, self.sched_step = int(sd["step"]), int(sd["sched_step"])
 
     def projector_state_dict(self, grads=False):
@@ -702,37 +594,3 @@ def synthetic_engine(cfg, device="cuda", seed=0, **kw):
     torch.manual_seed(seed + 2)
     proj = MLPProjector(cfg.vision.hidden_size, cfg.text.hidden_size, cfg.expansion_factor, device=device)
     return Stage2Engine(vision, llm, proj, **kw)
-
-
-def reduce_scatter_(out_shard, flat, world, rank, group=None):
-    """Sum of `flat` over ranks, this rank's contiguous shard into out_shard (RCCL reduce-scatter; gloo
-    has none: all-reduce and slice)."""
-    if dist.get_backend(group) == "gloo":
-        t = flat.float()            # gloo has no bf16 sum: fp32 sum of the bf16 values, one rounding
-        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-        n = out_shard.numel()
-        out_shard.copy_(t[rank * n:(rank + 1) * n])
-    else:
-        dist.reduce_scatter_tensor(out_shard, flat, op=dist.ReduceOp.SUM, group=group)
-    return out_shard
-
-
-def all_reduce_sum_(t, group=None):
-    """Sum of the bf16 tensor `t` over ranks, in place: the same bits on every rank."""
-    if dist.get_backend(group) == "gloo":
-        f = t.float()               # gloo has no bf16 sum: fp32 sum of the bf16 values, one rounding
-        dist.all_reduce(f, op=dist.ReduceOp.SUM, group=group)
-        t.copy_(f)
-    else:
-        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
-    return t
-
-
-def all_gather_(flat, shard, world, group=None):
-    if dist.get_backend(group) == "gloo":
-        parts = [torch.empty(shard.shape, dtype=torch.float32, device=shard.device) for _ in range(world)]
-        dist.all_gather(parts, shard.float(), group=group)     # bf16 -> fp32 -> bf16 is exact
-        flat.copy_(torch.cat(parts))
-    else:
-        dist.all_gather_into_tensor(flat, shard, group=group)
-    return flat
